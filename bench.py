@@ -23,7 +23,14 @@ says ``"backend": "gloo"``). A rank whose process group does not hold exactly N 
 non-zero.
 
 Scaling is WEAK: each GPU processes 8192 samples per step; ``value`` is the whole-job
-samples/s. Data are synthetic (random inputs / labels of the config's shape), weights random.
+samples/s. Data are synthetic (random inputs / labels of the config's shape), weights random,
+all from fixed seeds: the same arguments give the same inputs on every run.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the one JSON result line.
+``--dump-outputs DIR`` also writes what the last timed step left (costs, update ratios, parameters)
+as ``DIR/<name>.npy`` (see ``_dump_outputs``). ``--full`` is where anything measured beyond the
+headline figure runs; there is nothing of that kind at present (every other model or precision is
+a ``--config`` of its own), so today it changes nothing.
 """
 from __future__ import annotations
 
@@ -174,6 +181,36 @@ def _emit(args, cfg, world, elapsed, costs, batch, ctx, trainer=None) -> None:
         os.write(_JSON_FD, (line + "\n").encode())
 
 
+DUMP_PARAM_BYTES = 48 << 20  # all parameter files of one --dump-outputs together (a dump stays under 64 MB)
+DUMP_SAMPLE_SEED = 2024
+
+
+def _dump_outputs(out_dir: str, model, costs, ratios) -> None:
+    """``--dump-outputs DIR``: what a caller of the timed path holds after its last timed step, as
+    ``DIR/<name>.npy`` — ``costs`` (fp64, one per timed step, the last step's last),
+    ``weight_upd_ratio`` (fp64, the last row the timed steps recorded) and ``param_NN`` (the model's
+    parameters in ``model.params`` order, fp32, or fp64 for an fp64 model). A parameter above its
+    share of the size cap is stored as a fixed sample: the same seeded flat indices on every run.
+    On the fused engine two runs of one build give the same parameters and ratios bit for bit; the
+    reported cost is folded with float atomics, so it repeats to fp32 rounding (~1e-8 relative)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "costs.npy"), np.asarray(costs, dtype=np.float64))
+    if ratios is not None:
+        np.save(os.path.join(out_dir, "weight_upd_ratio.npy"),
+                np.asarray([float("nan") if r is None else r for r in ratios], dtype=np.float64))
+    params = [p.detach() for p in model.params]
+    g = torch.Generator(device="cpu").manual_seed(DUMP_SAMPLE_SEED)
+    for i, p in enumerate(params):
+        keep = torch.float64 if p.dtype == torch.float64 else torch.float32
+        cap = DUMP_PARAM_BYTES // keep.itemsize // len(params)
+        flat = p.reshape(-1)
+        if flat.numel() > cap:
+            flat = flat[torch.randint(0, flat.numel(), (cap,), generator=g).to(flat.device)]
+        np.save(os.path.join(out_dir, f"param_{i:02d}.npy"), flat.to("cpu", keep).numpy())
+    log(f"outputs of the last timed step written to {out_dir}")
+
+
 def _bench_autograd(args, cfg, model, ctx, batch, local) -> int:
     """The reference epoch body (BASELINE.md method C: forward with dropout, CE, L2, backward,
     optimizer step, update ratios on progress epochs) through the autograd engine on the GPU."""
@@ -217,7 +254,10 @@ def _bench_autograd(args, cfg, model, ctx, batch, local) -> int:
         run(e)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - start
-    _emit(args, cfg, 1, elapsed, [float(c) for c in costs[args.warmup:]], batch, ctx)
+    timed = [float(c) for c in costs[args.warmup:]]
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, model, timed, None)
+    _emit(args, cfg, 1, elapsed, timed, batch, ctx)
     return 0
 
 
@@ -253,6 +293,9 @@ def _bench_train(args, cfg, model, ctx, batch) -> int:
     elapsed = (t_b - t_a).total_seconds()
     import shutil
     shutil.rmtree(os.environ["PZ_MODELS_DIR"], ignore_errors=True)
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, model, [pts[e]["cost"] for e in range(args.warmup + 1, total + 1)],
+                      pts[total]["weight_upd_ratio"])
     _emit(args, cfg, 1, elapsed, [pts[e]["cost"] for e in range(args.warmup + 1, total + 1)], batch, ctx)
     return 0
 
@@ -270,6 +313,12 @@ def main(argv=None) -> int:
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--weight-algo", default="xavier")
     ap.add_argument("--n-data", type=int, default=None, help="synthetic dataset rows (default 2 x batch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left (costs, update ratios, parameters) "
+                         "as DIR/<name>.npy; same arguments, same inputs: two builds compare output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond its headline figure (nothing at present: "
+                         "every other model / precision is a --config of its own)")
     raw = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(raw)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -340,7 +389,12 @@ def main(argv=None) -> int:
     elapsed = time.perf_counter() - start
     elapsed = ctx.all_reduce_scalar_max(elapsed)
 
-    costs = [c for _, c, _, _ in trainer.drain()]
+    drained = trainer.drain()
+    costs = [c for _, c, _, _ in drained]
+    if args.dump_outputs and rank == 0:
+        timed = [d for d in drained if d[0] >= args.warmup]
+        _dump_outputs(args.dump_outputs, model, [c for _, c, _, _ in timed],
+                      next((r for _, _, r, _ in reversed(timed) if r is not None), None))
     if os.environ.get("PZ_BENCH_SERIES") == "1" and rank == 0:  # per-step GPU periods (the trainer's events)
         log("step periods (ms): " + " ".join(f"{trainer.step_ms[e]:.3f}" for e in sorted(trainer.step_ms)))
     _emit(args, cfg, world, elapsed, costs, batch, ctx, trainer)

@@ -14,7 +14,6 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-SHIMS = os.path.join(ROOT, "tests", "_shims")
 
 
 def pytest_configure(config):
