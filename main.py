@@ -5,6 +5,7 @@ existing clients, its test-suite and the dashboard work unchanged:
 
     GET  /              -> 307 /dashboard            GET /dashboard      -> HTML page
     POST /model/        create + serialize            POST /output/       inference (+ cost)
+    POST /predict/      batch inference, outputs only (models stay loaded between requests)
     PUT  /train/        202, training in background   (409 while that model is training)
     GET  /progress/     progress / avg cost / status  GET /stats/         training diagnostics
     DELETE /model/      204
@@ -21,7 +22,9 @@ from __future__ import annotations
 
 import logging
 import os
+import threading
 from asyncio import Lock, create_task
+from collections import OrderedDict
 from contextlib import asynccontextmanager
 from typing import Dict
 
@@ -35,6 +38,7 @@ from pydantic import BaseModel, Field
 
 from neural_net_model import NeuralNetworkModel
 from penr_oz_neural_network_torch_amd.parallel import service
+from penr_oz_neural_network_torch_amd.utils import checkpoint as ckpt
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -107,6 +111,11 @@ class CreateModelRequest(ModelRequest):
 
 class ActivationRequest(ModelRequest):
     input: InputItem = Field(..., description="The input data, an InputItem.")
+
+
+class PredictRequest(ModelRequest):
+    inputs: list = Field(..., description="One input vector (1D) or a batch of them (2D); id sequences for "
+                                          "embedding models.")
 
 
 class TrainingRequest(ModelRequest):
@@ -194,6 +203,76 @@ def compute_model_output(body: ActivationRequest = Body(..., openapi_examples={
     return {"output_vector": output, "cost": cost}
 
 
+# POST /predict/ keeps the models it served loaded: a small LRU by model id. Every request checks
+# the entry against the checkpoint file's (mtime, size), so a checkpoint rewritten by a training
+# (or a re-created model) is loaded again; DELETE /model/ evicts.
+PREDICT_CACHE_SIZE = 4
+_predict_cache: "OrderedDict[str, tuple]" = OrderedDict()
+_predict_cache_lock = threading.Lock()
+
+
+def _evict_cached_model(model_id: str) -> None:
+    with _predict_cache_lock:
+        _predict_cache.pop(model_id, None)
+
+
+def _cached_model(model_id: str) -> NeuralNetworkModel:
+    try:
+        st = os.stat(ckpt.model_path(model_id))
+    except FileNotFoundError:
+        _evict_cached_model(model_id)
+        raise KeyError(f"Model {model_id} not created yet.")
+    stamp = (st.st_mtime_ns, st.st_size)
+    with _predict_cache_lock:
+        entry = _predict_cache.get(model_id)
+        if entry is not None and entry[0] == stamp:
+            _predict_cache.move_to_end(model_id)
+            return entry[1]
+    model = NeuralNetworkModel.deserialize(model_id)  # (stamp taken first: a later rewrite reloads again)
+    with _predict_cache_lock:
+        _predict_cache[model_id] = (stamp, model)
+        _predict_cache.move_to_end(model_id)
+        while len(_predict_cache) > PREDICT_CACHE_SIZE:
+            _predict_cache.popitem(last=False)
+    return model
+
+
+def _check_predict_inputs(model: NeuralNetworkModel, inputs: list) -> None:
+    """1-D or 2-D, rectangular, and as wide as the model's first linear layer (ValueError -> 400)."""
+    if not inputs:
+        raise ValueError("inputs must not be empty")
+    batch = isinstance(inputs[0], list)
+    rows = inputs if batch else [inputs]
+    if any(not isinstance(r, list) for r in rows) or any(isinstance(v, list) for v in rows[0]):
+        raise ValueError("inputs must be one vector (1D) or a batch of vectors (2D)")
+    width = len(rows[0])
+    if width == 0 or any(len(r) != width for r in rows):
+        raise ValueError("every input row must have the same, non-zero length")
+    first = next((layer for layer in model.layers if layer.weights is not None), None)
+    if first is not None and first.algo == "linear" and width != first.weights.shape[0]:
+        raise ValueError(f"model {model.model_id} takes {first.weights.shape[0]} inputs per row, got {width}")
+
+
+PREDICT_EXAMPLES = {
+    "single": {"summary": "One vector", "description": "One 9-cell board; the response holds one output vector.",
+               "value": {"model_id": "test", "inputs": EXAMPLES[2]["activation_vector"]}},
+    "batch": {"summary": "A batch", "description": "Three boards in one request; one output vector per row.",
+              "value": {"model_id": "test", "inputs": [ex["activation_vector"] for ex in EXAMPLES[:3]]}},
+}
+
+
+@app.post("/predict/")
+def predict_model_output(body: PredictRequest = Body(..., openapi_examples=PREDICT_EXAMPLES)):
+    model_id = body.model_id
+    log.info(f"Requesting prediction for model {model_id}")
+    model = _cached_model(model_id)
+    _check_predict_inputs(model, body.inputs)
+    try:
+        return {"output_vectors": model.predict(body.inputs)}
+    except IndexError as e:  # an embedding id outside the vocabulary is a bad request
+        raise ValueError(str(e))
+
+
 # active training sessions by model id (one event loop, so a plain dict is safe), and the ids
 # whose PUT /train/ is still loading the checkpoint (between the 409 check and the task start)
 model_locks: Dict[str, Lock] = {}
@@ -264,6 +343,7 @@ def model_stats(model_id: str = ModelIdQuery(...)):
 def delete_model(model_id: str = ModelIdQuery(...)):
     log.info(f"Requesting deletion of model {model_id}")
     NeuralNetworkModel.delete(model_id)
+    _evict_cached_model(model_id)
     return Response(status_code=204)
 
 

@@ -448,6 +448,62 @@ int64_t gemm_path_op(const Tensor& A, bool a_kc, const Tensor& B, bool b_kc, con
   return pz::gemm_path(p);
 }
 
+// -------------------------------------------------------------- skinny-batch forward GEMM
+// out[M,N] = act(x[M,K] @ w[K,N] + bias), 1 <= M <= 16 (gemm_skinny.hip). Structural mistakes
+// (ranks, shapes, dtypes, devices) raise; *eligible says whether the kernel takes the operands.
+pz::SkinnyArgs skinny_args(const Tensor& x, const Tensor& w, const Tensor& out, const optional<Tensor>& bias, int64_t act) {
+  check_dev(x, "x");
+  check_dev(w, "w");
+  check_dev(out, "out");
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2, "pz::gemm_skinny: 2-D operands expected");
+  TORCH_CHECK(x.device() == w.device() && x.device() == out.device(), "pz::gemm_skinny: operands on one device");
+  TORCH_CHECK(x.scalar_type() == w.scalar_type(), "pz::gemm_skinny: x and w must have one dtype");
+  TORCH_CHECK(x.size(1) == w.size(0) && out.size(0) == x.size(0) && out.size(1) == w.size(1),
+              "pz::gemm_skinny: shapes x[M,K] w[K,N] out[M,N]");
+  pz::SkinnyArgs a{};
+  a.x = x.data_ptr();
+  a.w = w.data_ptr();
+  a.out = out.data_ptr();
+  a.M = static_cast<int>(x.size(0));
+  a.K = static_cast<int>(x.size(1));
+  a.N = static_cast<int>(w.size(1));
+  a.ldx = x.stride(0);
+  a.ldw = w.stride(0);
+  a.ldo = out.stride(0);
+  a.in_dtype = x.scalar_type() == at::kBFloat16 ? pz::DT_BF16 : x.scalar_type() == at::kFloat ? pz::DT_F32 : -1;
+  a.out_dtype = out.scalar_type() == at::kBFloat16 ? pz::DT_BF16 : out.scalar_type() == at::kFloat ? pz::DT_F32 : -1;
+  a.act = static_cast<int>(act);
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == at::kFloat && bias->is_contiguous() && bias->numel() == a.N,
+                "pz::gemm_skinny: bias must be a contiguous fp32 [N] GPU tensor");
+    a.bias = bias->data_ptr<float>();
+  }
+  return a;
+}
+
+bool skinny_ok(const pz::SkinnyArgs& a, const Tensor& x, const Tensor& w, const Tensor& out) {
+  return x.size(0) <= 16 && x.stride(1) == 1 && w.stride(1) == 1 && out.stride(1) == 1 && pz::skinny_eligible(a);
+}
+
+bool gemm_skinny_eligible_op(const Tensor& x, const Tensor& w, const Tensor& out) {
+  return skinny_ok(skinny_args(x, w, out, c10::nullopt, 0), x, w, out);
+}
+
+void gemm_skinny_op(const Tensor& x, const Tensor& w, const Tensor& out, const optional<Tensor>& bias, int64_t act) {
+  auto a = skinny_args(x, w, out, bias, act);
+  TORCH_CHECK(skinny_ok(a, x, w, out),
+              "pz::gemm_skinny: not eligible (1 <= M <= 16, bf16 / fp32 operands, unit inner strides, W rows and "
+              "leading dimension multiples of 16 B, W 16-B aligned); nothing was launched");
+  at::Tensor ws;  // split-K slabs: from the caching allocator, stream-ordered reuse is safe
+  const int64_t ws_floats = pz::skinny_ws_floats(a);
+  if (ws_floats > 0) {
+    ws = at::empty({ws_floats}, x.options().dtype(at::kFloat));
+    a.ws = ws.data_ptr<float>();
+    a.tickets = split_counters(pz::skinny_plan(a.K, a.N, a.in_dtype).strips, x.device());
+  }
+  PZ_HIP_CHECK(pz::gemm_skinny(a, cur_stream(x)));
+}
+
 // ------------------------------------------------------------------------------ elementwise
 void stage_fwd_op(const Tensor& x, const Tensor& y, at::IntArrayRef ei, at::ArrayRef<double> ef) {
   check_dev(x, "x");
@@ -1022,6 +1078,8 @@ TORCH_LIBRARY(pz, m) {
         "Tensor(f!)? amax, bool adam, float lr, float beta1, float beta2, float eps, float bias_c1, "
         "float bias_c2_sqrt, float grad_scale, float l2, Tensor? hp=None, Tensor? epoch=None, int stats_every=1) -> ()");
   m.def("gemm_path(Tensor A, bool a_kc, Tensor B, bool b_kc, Tensor C, int M, int N, int K) -> int");
+  m.def("gemm_skinny(Tensor x, Tensor w, Tensor(a!) out, Tensor? bias, int act) -> ()");
+  m.def("gemm_skinny_eligible(Tensor x, Tensor w, Tensor out) -> bool");
   m.def("gemm_pair_split(Tensor A0, Tensor B0, Tensor C0, Tensor A1, Tensor B1, Tensor C1, int M0, int N0, int M1, "
         "int N1, int K, int engine=0) -> int");
   m.def("gemm_pair(Tensor A0, Tensor B0, Tensor(a!) C0, Tensor A1, Tensor B1, Tensor(b!) C1, int M0, int N0, int M1, "
@@ -1079,6 +1137,8 @@ TORCH_LIBRARY(pz, m) {
 TORCH_LIBRARY_IMPL(pz, CUDA, m) {
   m.impl("gemm", TORCH_FN(gemm_op));
   m.impl("gemm_path", TORCH_FN(gemm_path_op));
+  m.impl("gemm_skinny", TORCH_FN(gemm_skinny_op));
+  m.impl("gemm_skinny_eligible", TORCH_FN(gemm_skinny_eligible_op));
   m.impl("gemm_pair_split", TORCH_FN(gemm_pair_split_op));
   m.impl("gemm_pair", TORCH_FN(gemm_pair_op));
   m.impl("gemm_update", TORCH_FN(gemm_update_op));

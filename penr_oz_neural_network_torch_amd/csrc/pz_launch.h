@@ -143,4 +143,32 @@ hipError_t gemm_pair(const GemmArgs& a, const GemmArgs& b, hipStream_t stream);
 // exposed for tests / benchmarks: which path gemm() would take
 int gemm_path(const GemmArgs& args);  // 0 = generic VALU, 1 = MFMA bf16 / fp8, 2 = MFMA fp32 / fp64
 
+// Skinny-batch forward GEMM of the inference path (gemm_skinny.hip): out[M][N] = act(x[M][K] ·
+// W[K][N] + bias), 1 <= M <= 16, W N-contiguous, x of W's type (bf16 / fp32), fp32 accumulation.
+// A separate op: gemm() never selects it.
+struct SkinnyArgs {
+  const void* x;      // [M][ldx]
+  const void* w;      // [K][ldw]
+  void* out;          // [M][ldo]
+  const float* bias;  // [N] fp32 or null
+  int M, N, K;
+  int64_t ldx, ldw, ldo;  // elements
+  int in_dtype;       // DT_BF16 or DT_F32 (x and W)
+  int out_dtype;      // DT_BF16 or DT_F32
+  int act;            // Act, applied after the bias
+  float* ws;          // skinny_ws_floats() fp32 partial slabs (slices > 1)
+  int* tickets;       // [strips], zero; reset by each strip's last arriver
+};
+struct SkinnyPlan {
+  int strips;      // column strips of strip_cols columns (grid.x)
+  int strip_cols;
+  int slices;      // K slices over workgroups (grid.y)
+  int slice_len;   // K rows per slice
+};
+SkinnyPlan skinny_plan(int K, int N, int dtype);  // never a function of M
+int skinny_bucket(int M);                         // compile-time row count the call runs with: 1, 2, 4, 8, 16
+bool skinny_eligible(const SkinnyArgs& a);
+int64_t skinny_ws_floats(const SkinnyArgs& a);
+hipError_t gemm_skinny(const SkinnyArgs& a, hipStream_t stream);  // hipErrorInvalidValue: not eligible, nothing launched
+
 }  // namespace pz

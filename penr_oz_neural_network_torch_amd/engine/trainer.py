@@ -659,6 +659,7 @@ class FusedTrainer(Fp8Policy):
         ``lr_schedule(epoch) -> lr`` (the learning rate :meth:`step` will be called with) enables
         hipGraph replay: the per-epoch optimizer hyper-parameters are tabulated on the device
         once, so a captured step needs nothing from the host but a replay."""
+        self.model._predictor = None  # the steps rewrite the masters: predict() re-copies them
         self._alloc_progress(epochs)
         self._invalidate_graphs()
         self._plan = None

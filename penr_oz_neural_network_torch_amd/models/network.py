@@ -119,6 +119,7 @@ class NeuralNetworkModel(MultiLayerPerceptron):
         self.precision: Precision = resolve_precision(dtype)
         self.device = _effective_device(device)
         self._param_store = None
+        self._predictor = None  # lazily built FusedPredictor (False: this model has none); see predict
         self.optimizer: torch.optim.Optimizer | None = None
         if self.params:
             if self.weights:
@@ -151,6 +152,7 @@ class NeuralNetworkModel(MultiLayerPerceptron):
 
     def _place(self) -> None:
         """Move the (fp64, CPU) parameters into one flat buffer on the model's device/precision."""
+        self._predictor = None  # its weight copies belong to the previous placement
         if self.is_reference_runtime or not self.params:
             self._param_store = None
             return
@@ -288,6 +290,40 @@ class NeuralNetworkModel(MultiLayerPerceptron):
             out = out.float()
         return out.tolist(), cost.item() if cost.numel() > 0 else None
 
+    def predict(self, input_data: list) -> list:
+        """Outputs only, forward-only: what ``compute_output(input_data)[0]`` returns, without a
+        cost or a target, layers in eval mode, nothing recorded for autograd.
+
+        GPU models run the fused forward schedule of :class:`..engine.predictor.FusedPredictor`
+        (GEMM-dtype weight copies made once, the skinny-batch GEMM below 64 rows, fused bias /
+        activation epilogues); it is built on first use and dropped whenever the parameters may
+        have changed (``train``, ``set_model_data``, re-placement), so it never serves stale
+        weights. Models it cannot schedule (``float64``, unusual layer orders), CPU models and the
+        reference runtime run the layer loop under ``no_grad`` — there the result is bit-identical
+        to ``compute_output``'s."""
+        x = self._input_tensor(input_data)
+        with torch.no_grad():
+            predictor = self._fused_predictor() if self.on_gpu else None
+            if predictor is not None:
+                for layer in self.layers:
+                    layer.training = False
+                out = predictor.forward(x)
+            else:
+                out = self._forward(x, None)[0][-1].detach()
+                if out.dtype == torch.bfloat16:
+                    out = out.float()
+        return out.tolist()
+
+    def _fused_predictor(self):
+        if self._predictor is None:
+            from ..engine.predictor import FusedPredictor, UnsupportedModel
+            try:
+                self._predictor = FusedPredictor(self)
+            except UnsupportedModel as e:
+                log.info(f"Model {self.model_id}: fused predictor unavailable ({e}); predicting through the layers")
+                self._predictor = False
+        return self._predictor or None
+
     def _forward(self, input_tensor: Tensor, target: list, dropout_rate=0.0) -> Tuple[list[Tensor], Tensor]:
         target_specified = target is not None and (isinstance(target, Tensor) or all(t is not None for t in target))
         gpu = self.on_gpu
@@ -362,6 +398,7 @@ class NeuralNetworkModel(MultiLayerPerceptron):
 
         hp = dict(epochs=epochs, learning_rate=learning_rate, sample_size=sample_size, decay_rate=decay_rate,
                   dropout_rate=dropout_rate, l2_lambda=l2_lambda)
+        self._predictor = None  # the masters change from here on: predict rebuilds its weight copies
         try:
             trainer = self._fused_trainer() if self.on_gpu else None
             if trainer is not None:
@@ -381,6 +418,8 @@ class NeuralNetworkModel(MultiLayerPerceptron):
             except Exception:  # pragma: no cover - keep the original error
                 log.exception(f"Model {self.model_id}: could not persist the failed status")
             raise
+        finally:
+            self._predictor = None  # (a predict during the training built one on half-trained weights)
 
         self.status = "Trained"
         log.info(f"Model {self.model_id}: Done training for {epochs} epochs.")
@@ -411,6 +450,7 @@ class NeuralNetworkModel(MultiLayerPerceptron):
         (identical) optimizer step — equivalent to one process training on the whole sample."""
         ctx = context or self._dp_context()
         world, rank = ctx.world_size, ctx.rank
+        self._predictor = None
         from . import layers as _layers
         _layers.set_bn_sync(self.layers, ctx if world > 1 else None)  # synchronised batchnorm statistics
         try:
@@ -554,6 +594,7 @@ class NeuralNetworkModel(MultiLayerPerceptron):
     def _train_fused(self, trainer, data, epochs, learning_rate, sample_size, decay_rate, dropout_rate, l2_lambda):
         """Same schedule as :meth:`_train_autograd`, enqueued on the GPU without host syncs;
         costs / ratios / timestamps come back in :meth:`FusedTrainer.drain`."""
+        self._predictor = None
         trainer.load_data(data)
         trainer.begin(epochs, lr_schedule=lambda e: learning_rate * decay_rate ** e)
         every = max(1, epochs // MAX_PROGRESS_POINTS)

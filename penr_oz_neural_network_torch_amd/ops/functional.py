@@ -183,6 +183,30 @@ def gemm_path(a: Tensor, a_kc: bool, b: Tensor, b_kc: bool, out: Tensor) -> str:
     return {1: "mfma", 2: "mfma_wide"}.get(path, "generic")  # mfma_wide: fp32 / fp64 matrix cores
 
 
+SKINNY_MAX_ROWS = 16
+
+
+def gemm_skinny_eligible(x: Tensor, w: Tensor, out: Tensor) -> bool:
+    """Whether :func:`gemm_skinny` takes these operands: GPU tensors, ``x [M, K]`` and ``w [K, N]``
+    of one dtype (bf16 / fp32), ``1 <= M <= 16``, ``out [M, N]`` bf16 / fp32, unit inner strides,
+    ``w``'s row bytes and leading dimension multiples of 16 B and its base 16-B aligned."""
+    if not (x.is_cuda and w.is_cuda and out.is_cuda) or x.dim() != 2 or w.dim() != 2 or out.dim() != 2:
+        return False
+    if x.dtype != w.dtype or x.shape[1] != w.shape[0] or out.shape != (x.shape[0], w.shape[1]):
+        return False
+    return bool(_ops().gemm_skinny_eligible(x, w, out))
+
+
+def gemm_skinny(x: Tensor, w: Tensor, out: Tensor, *, bias: Tensor | None = None, act: int = ACT_NONE) -> Tensor:
+    """``out[M,N] = act(x[M,K] @ w[K,N] + bias)`` for ``1 <= M <= 16``: the forward-only weight-
+    streaming kernel of the inference path (csrc/gemm_skinny.hip). ``w`` in the layers' ``[in, out]``
+    layout, fp32 ``bias``, fp32 accumulation in a fixed order (bit-reproducible, and a row's result
+    does not depend on the rows sent with it). Operands that are not
+    :func:`gemm_skinny_eligible` raise; nothing is launched for them."""
+    _ops().gemm_skinny(x, w, out, bias, act)
+    return out
+
+
 def _as_2d(x: Tensor) -> tuple[Tensor, tuple]:
     lead = x.shape[:-1]
     return x.reshape(-1, x.shape[-1]).contiguous(), lead
@@ -489,5 +513,5 @@ def tensor_summary(t: Tensor, algo: str | None, bins: int) -> dict:
     return out
 
 
-__all__ = ["gemm", "gemm_path", "linear", "activation", "dropout", "softmax", "cross_entropy", "mse_loss",
+__all__ = ["gemm", "gemm_path", "gemm_skinny", "gemm_skinny_eligible", "linear", "activation", "dropout", "softmax", "cross_entropy", "mse_loss",
            "batchnorm", "embedding", "tensor_summary", "epi_spec", "new_seed"]
