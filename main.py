@@ -116,6 +116,11 @@ class ActivationRequest(ModelRequest):
 class PredictRequest(ModelRequest):
     inputs: list = Field(..., description="One input vector (1D) or a batch of them (2D); id sequences for "
                                           "embedding models.")
+    # (the OpenAPI example of this option is the field's own: the request-body examples stay the two above)
+    weights: str | None = Field(None, examples=["fp8"],
+                                description="Weight format to predict from. Omitted: the model's own precision. 'fp8': "
+                                            "weight-only e4m3 copies, one power-of-two scale per output column (GPU "
+                                            "models with dtype bfloat16 or fp8; anything else answers 400)")
 
 
 class TrainingRequest(ModelRequest):
@@ -268,7 +273,9 @@ def predict_model_output(body: PredictRequest = Body(..., openapi_examples=PREDI
     model = _cached_model(model_id)
     _check_predict_inputs(model, body.inputs)
     try:
-        return {"output_vectors": model.predict(body.inputs)}
+        if body.weights is None:
+            return {"output_vectors": model.predict(body.inputs)}
+        return {"output_vectors": model.predict(body.inputs, weights=body.weights)}
     except IndexError as e:  # an embedding id outside the vocabulary is a bad request
         raise ValueError(str(e))
 

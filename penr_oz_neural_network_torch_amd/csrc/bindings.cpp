@@ -504,6 +504,68 @@ void gemm_skinny_op(const Tensor& x, const Tensor& w, const Tensor& out, const o
   PZ_HIP_CHECK(pz::gemm_skinny(a, cur_stream(x)));
 }
 
+// out[M,N] = act(scale[n] * (x[M,K] @ w8[K,N]) + bias), w8 a float8_e4m3fn tensor with one
+// power-of-two fp32 scale per column (gemm_skinny_w8.hip). Structural mistakes raise, as above.
+pz::SkinnyW8Args skinny_w8_args(const Tensor& x, const Tensor& w8, const Tensor& scale, const Tensor& out,
+                                const optional<Tensor>& bias, int64_t act) {
+  check_dev(x, "x");
+  check_dev(w8, "w8");
+  check_dev(scale, "scale");
+  check_dev(out, "out");
+  TORCH_CHECK(x.dim() == 2 && w8.dim() == 2 && out.dim() == 2, "pz::gemm_skinny_w8: 2-D operands expected");
+  TORCH_CHECK(x.device() == w8.device() && x.device() == out.device() && x.device() == scale.device(),
+              "pz::gemm_skinny_w8: operands on one device");
+  TORCH_CHECK(w8.scalar_type() == at::kFloat8_e4m3fn, "pz::gemm_skinny_w8: w8 must be a float8_e4m3fn tensor");
+  TORCH_CHECK(x.size(1) == w8.size(0) && out.size(0) == x.size(0) && out.size(1) == w8.size(1),
+              "pz::gemm_skinny_w8: shapes x[M,K] w8[K,N] out[M,N]");
+  pz::SkinnyW8Args a{};
+  a.M = static_cast<int>(x.size(0));
+  a.K = static_cast<int>(x.size(1));
+  a.N = static_cast<int>(w8.size(1));
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.dim() == 1 && scale.numel() == a.N,
+              "pz::gemm_skinny_w8: scale must be a contiguous fp32 [N] GPU tensor");
+  a.x = x.data_ptr();
+  a.w8 = static_cast<const uint8_t*>(w8.data_ptr());
+  a.scale = scale.data_ptr<float>();
+  a.out = out.data_ptr();
+  a.ldx = x.stride(0);
+  a.ldw = w8.stride(0);
+  a.ldo = out.stride(0);
+  a.in_dtype = x.scalar_type() == at::kBFloat16 ? pz::DT_BF16 : -1;
+  a.out_dtype = out.scalar_type() == at::kBFloat16 ? pz::DT_BF16 : out.scalar_type() == at::kFloat ? pz::DT_F32 : -1;
+  a.act = static_cast<int>(act);
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == at::kFloat && bias->is_contiguous() && bias->numel() == a.N,
+                "pz::gemm_skinny_w8: bias must be a contiguous fp32 [N] GPU tensor");
+    a.bias = bias->data_ptr<float>();
+  }
+  return a;
+}
+
+bool skinny_w8_ok(const pz::SkinnyW8Args& a, const Tensor& x, const Tensor& w8, const Tensor& out) {
+  return x.size(0) <= 16 && x.stride(1) == 1 && w8.stride(1) == 1 && out.stride(1) == 1 && pz::skinny_w8_eligible(a);
+}
+
+bool gemm_skinny_w8_eligible_op(const Tensor& x, const Tensor& w8, const Tensor& scale, const Tensor& out) {
+  return skinny_w8_ok(skinny_w8_args(x, w8, scale, out, c10::nullopt, 0), x, w8, out);
+}
+
+void gemm_skinny_w8_op(const Tensor& x, const Tensor& w8, const Tensor& scale, const Tensor& out,
+                       const optional<Tensor>& bias, int64_t act) {
+  auto a = skinny_w8_args(x, w8, scale, out, bias, act);
+  TORCH_CHECK(skinny_w8_ok(a, x, w8, out),
+              "pz::gemm_skinny_w8: not eligible (1 <= M <= 16, bf16 x, unit inner strides, W8 rows and leading "
+              "dimension multiples of 16 B, W8 16-B aligned); nothing was launched");
+  at::Tensor ws;  // split-K slabs: from the caching allocator, stream-ordered reuse is safe
+  const int64_t ws_floats = pz::skinny_w8_ws_floats(a);
+  if (ws_floats > 0) {
+    ws = at::empty({ws_floats}, x.options().dtype(at::kFloat));
+    a.ws = ws.data_ptr<float>();
+    a.tickets = split_counters(pz::skinny_w8_plan(a.K, a.N).strips, x.device());
+  }
+  PZ_HIP_CHECK(pz::gemm_skinny_w8(a, cur_stream(x)));
+}
+
 // ------------------------------------------------------------------------------ elementwise
 void stage_fwd_op(const Tensor& x, const Tensor& y, at::IntArrayRef ei, at::ArrayRef<double> ef) {
   check_dev(x, "x");
@@ -955,6 +1017,28 @@ void quantize_rows_op(const Tensor& x, const Tensor& out, const Tensor& qs, cons
                                  amax_clear.has_value() ? amax_clear->data_ptr<float>() : nullptr));
 }
 
+// w [K,N] fp32 -> out [K,N] e4m3 (same layout) + one power-of-two scale per column; amax is the
+// caller-zeroed fp32 [N] scratch of the column-amax phase (quant_cols.hip)
+void quantize_cols_op(const Tensor& w, const Tensor& out, const Tensor& scale, const Tensor& amax) {
+  check_dev(w, "w");
+  check_dev(out, "out");
+  check_dev(scale, "scale");
+  check_dev(amax, "amax");
+  TORCH_CHECK(w.scalar_type() == at::kFloat && w.dim() == 2 && (w.stride(1) == 1 || w.size(1) <= 1) && w.stride(0) >= w.size(1),
+              "pz::quantize_cols: fp32 [K,N] w with unit inner stride");
+  TORCH_CHECK(out.scalar_type() == at::kFloat8_e4m3fn && out.dim() == 2 && (out.stride(1) == 1 || out.size(1) <= 1) &&
+                  out.size(0) == w.size(0) && out.size(1) == w.size(1) && out.stride(0) >= out.size(1),
+              "pz::quantize_cols: out must be e4m3 [K,N]");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.numel() == w.size(1) &&
+                  amax.scalar_type() == at::kFloat && amax.is_contiguous() && amax.numel() == w.size(1),
+              "pz::quantize_cols: contiguous fp32 scale[N] and amax[N]");
+  TORCH_CHECK(w.device() == out.device() && w.device() == scale.device() && w.device() == amax.device(),
+              "pz::quantize_cols: operands on one device");
+  PZ_HIP_CHECK(pz::quantize_cols(w.data_ptr<float>(), w.stride(0), static_cast<int>(w.size(0)), static_cast<int>(w.size(1)),
+                                 static_cast<uint8_t*>(out.data_ptr()), out.stride(0), scale.data_ptr<float>(),
+                                 amax.data_ptr<float>(), cur_stream(w)));
+}
+
 void step_finalize_op(const optional<Tensor>& loss, double loss_div, const Tensor& stats_prev, const Tensor& stats_cur,
                       const Tensor& slot_numel, int64_t nslots, double l2, const Tensor& costs, int64_t epoch,
                       const Tensor& ratios, int64_t ratio_row, const optional<Tensor>& epoch_ctr, int64_t every,
@@ -1080,6 +1164,8 @@ TORCH_LIBRARY(pz, m) {
   m.def("gemm_path(Tensor A, bool a_kc, Tensor B, bool b_kc, Tensor C, int M, int N, int K) -> int");
   m.def("gemm_skinny(Tensor x, Tensor w, Tensor(a!) out, Tensor? bias, int act) -> ()");
   m.def("gemm_skinny_eligible(Tensor x, Tensor w, Tensor out) -> bool");
+  m.def("gemm_skinny_w8(Tensor x, Tensor w8, Tensor scale, Tensor(a!) out, Tensor? bias, int act) -> ()");
+  m.def("gemm_skinny_w8_eligible(Tensor x, Tensor w8, Tensor scale, Tensor out) -> bool");
   m.def("gemm_pair_split(Tensor A0, Tensor B0, Tensor C0, Tensor A1, Tensor B1, Tensor C1, int M0, int N0, int M1, "
         "int N1, int K, int engine=0) -> int");
   m.def("gemm_pair(Tensor A0, Tensor B0, Tensor(a!) C0, Tensor A1, Tensor B1, Tensor(b!) C1, int M0, int N0, int M1, "
@@ -1128,6 +1214,7 @@ TORCH_LIBRARY(pz, m) {
   m.def("quant_transpose(Tensor w, Tensor(a!) out, Tensor(b!) qs, Tensor? amax=None, Tensor(c!)? amax_clear=None) -> ()");
   m.def("quantize_rows(Tensor x, Tensor(a!) out, Tensor(c!) qs, Tensor(b!)? amax, Tensor? amax_in=None, "
         "Tensor(d!)? amax_clear=None) -> ()");
+  m.def("quantize_cols(Tensor w, Tensor(a!) out, Tensor(b!) scale, Tensor(c!) amax) -> ()");
   m.def("format_json_array(Tensor t, int level) -> str");
   m.def("repr_double(float x) -> str");
   m.def("scan_json_arrays(str path, str key) -> (str, Tensor, Tensor)");
@@ -1139,6 +1226,8 @@ TORCH_LIBRARY_IMPL(pz, CUDA, m) {
   m.impl("gemm_path", TORCH_FN(gemm_path_op));
   m.impl("gemm_skinny", TORCH_FN(gemm_skinny_op));
   m.impl("gemm_skinny_eligible", TORCH_FN(gemm_skinny_eligible_op));
+  m.impl("gemm_skinny_w8", TORCH_FN(gemm_skinny_w8_op));
+  m.impl("gemm_skinny_w8_eligible", TORCH_FN(gemm_skinny_w8_eligible_op));
   m.impl("gemm_pair_split", TORCH_FN(gemm_pair_split_op));
   m.impl("gemm_pair", TORCH_FN(gemm_pair_op));
   m.impl("gemm_update", TORCH_FN(gemm_update_op));
@@ -1164,6 +1253,7 @@ TORCH_LIBRARY_IMPL(pz, CUDA, m) {
   m.impl("scale_update", TORCH_FN(scale_update_op));
   m.impl("quant_transpose", TORCH_FN(quant_transpose_op));
   m.impl("quantize_rows", TORCH_FN(quantize_rows_op));
+  m.impl("quantize_cols", TORCH_FN(quantize_cols_op));
 }
 
 TORCH_LIBRARY_IMPL(pz, CPU, m) {

@@ -281,6 +281,12 @@ hipError_t quant_transpose(const float* w, int64_t ldw, int K, int N, uint8_t* o
 hipError_t quantize_rows(const void* x, int dtype, int64_t ldx, int rows, int cols, uint8_t* out, int64_t ldo,
                          float* qs, float* amax, hipStream_t s, int fmt = 0, const float* amax_in = nullptr,
                          float* amax_clear = nullptr);
+// weight-only inference (quant_cols.hip): W [K][N] fp32 (row stride ldw) -> W8 [K][N] e4m3 (row
+// stride ldo, same layout) with one power-of-two scale per column: scale[n] = 2^e, e the smallest
+// exponent (not below -126) with max_k |W[k][n]| <= 448 * 2^e (1 for an all-zero column), W8 =
+// e4m3_rne(clamp(W * 2^-e, +-448)). amax [N] is the caller-zeroed scratch of phase one.
+hipError_t quantize_cols(const float* w, int64_t ldw, int K, int N, uint8_t* out, int64_t ldo, float* scale,
+                         float* amax, hipStream_t s);
 
 // ------------------------------------------------------------------ collective footprint proxy
 // `wgs` resident workgroups for `us` microseconds, moving `chunk_bytes`-long scratch slices at one

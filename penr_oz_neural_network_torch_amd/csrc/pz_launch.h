@@ -171,4 +171,28 @@ bool skinny_eligible(const SkinnyArgs& a);
 int64_t skinny_ws_floats(const SkinnyArgs& a);
 hipError_t gemm_skinny(const SkinnyArgs& a, hipStream_t stream);  // hipErrorInvalidValue: not eligible, nothing launched
 
+// Weight-only quantised skinny GEMM (gemm_skinny_w8.hip): out[M][N] = act(scale[n] * (x[M][K] ·
+// W8[K][N]) + bias[n]), 1 <= M <= 16, x bf16, W8 OCP e4m3 bytes (N-contiguous), scale a power of
+// two per output column (quant_cols.hip), fp32 accumulation. A separate op: neither gemm() nor
+// gemm_skinny() ever selects it. Eligible: W8's row bytes and leading dimension multiples of 16 B,
+// its base 16-B aligned; everything else at its natural alignment.
+struct SkinnyW8Args {
+  const void* x;       // [M][ldx] bf16
+  const uint8_t* w8;   // [K][ldw] e4m3
+  const float* scale;  // [N] fp32, powers of two
+  void* out;           // [M][ldo]
+  const float* bias;   // [N] fp32 or null
+  int M, N, K;
+  int64_t ldx, ldw, ldo;  // elements
+  int in_dtype;        // x: DT_BF16 (anything else is refused)
+  int out_dtype;       // DT_BF16 or DT_F32
+  int act;             // Act, applied after scale and bias
+  float* ws;           // skinny_w8_ws_floats() fp32 partial slabs (slices > 1)
+  int* tickets;        // [strips], zero; reset by each strip's last arriver
+};
+SkinnyPlan skinny_w8_plan(int K, int N);  // never a function of M
+bool skinny_w8_eligible(const SkinnyW8Args& a);
+int64_t skinny_w8_ws_floats(const SkinnyW8Args& a);
+hipError_t gemm_skinny_w8(const SkinnyW8Args& a, hipStream_t stream);  // hipErrorInvalidValue: not eligible, nothing launched
+
 }  // namespace pz

@@ -25,6 +25,27 @@ kernel made for it. :class:`FusedPredictor` is the explicit forward schedule ins
 * hidden activations are in the GEMM dtype (bf16 for bf16 models — the fused trainer's numerics,
   also behind an embedding, whose lookups the layer loop keeps in fp32), the last linear stage's
   output and the softmax are fp32.
+
+Weight-only quantised inference, ``forward(x, weights="fp8")`` (bf16-compute models only): the same
+schedule on OCP e4m3 weight copies with one power-of-two scale per output column
+(``PF.quantize_cols`` of the fp32 masters; csrc/quant_cols.hip). Activations stay bf16, accumulation
+fp32, biases / batchnorm / embedding / softmax are untouched. The copies are built lazily, per layer,
+on the first fp8 request that needs them, so a predictor never asked for fp8 holds none:
+
+* below 64 rows a linear stage runs ``PF.gemm_skinny_w8`` (csrc/gemm_skinny_w8.hip) in chunks of at
+  most 16 rows; a layer that kernel does not take (an output width that is no multiple of 16, e.g.
+  72) runs the bf16 path above on a **dequantised bf16 copy** of that layer;
+* from 64 rows on, the tiled ``PF.gemm`` calls run on the dequantised bf16 copies.
+
+The scales being powers of two, ``w8 * scale`` is exactly representable in bf16 and every product
+of the e4m3 kernel is exact in fp32: whichever kernel runs computes the same function of the same
+weight values, so the row a caller gets back does not change its meaning with the batch size. A
+process that serves both regimes in fp8 holds 1 + 2 bytes per weight (e4m3 + dequantised bf16) on
+top of the default path's copies; one that only sends batches under 64 rows holds 1 byte per weight
+of the eligible layers. Measured (profiles/predict_w8_latency.txt): the e4m3 kernel beats the bf16
+one at 1 row on every layer shape tried and at every row count on an 8192 x 8192 layer, and is
+1.2-1.4x slower at 16 rows on layers of 16 Mi weights or fewer; the chunks still go through it, so
+that the memory held does not depend on the batch sizes a process happens to see.
 """
 from __future__ import annotations
 
@@ -58,6 +79,10 @@ class FusedPredictor:
         self.weights: dict[int, Tensor] = {}
         self.biases: dict[int, Tensor | None] = {}
         self._skinny_ok: dict[int, bool] = {}
+        # weights="fp8": e4m3 copies + column scales, their dequantised bf16 copies; built on demand
+        self.weights8: dict[int, tuple[Tensor, Tensor]] = {}
+        self.weights_deq: dict[int, Tensor] = {}
+        self._w8_ok: dict[int, bool] = {}
         gemms = [st for st in self.stages if st.kind == "gemm"]
         self.last_gemm = gemms[-1].index if gemms else -1
         with torch.no_grad():
@@ -67,9 +92,21 @@ class FusedPredictor:
                 self.biases[st.index] = store.view(st.seg_b) if st.seg_b is not None else None
 
     # ------------------------------------------------------------------------------------
-    def _linear(self, st, x: Tensor) -> Tensor:
-        w, bias = self.weights[st.index], self.biases[st.index]
-        k, n = w.shape
+    def _quantised(self, index: int) -> tuple[Tensor, Tensor]:
+        """(e4m3 copy, column scales) of one linear stage's fp32 master, built on first need."""
+        if index not in self.weights8:
+            self.weights8[index] = PF.quantize_cols(self.store.view(self.stages[index].seg_w))
+        return self.weights8[index]
+
+    def _dequantised(self, index: int) -> Tensor:
+        """bf16 copy of the quantised weights (exact: the scales are powers of two), built on first need."""
+        if index not in self.weights_deq:
+            self.weights_deq[index] = PF.dequantize_cols(*self._quantised(index), dtype=self.compute).contiguous()
+        return self.weights_deq[index]
+
+    def _linear(self, st, x: Tensor, fp8: bool = False) -> Tensor:
+        bias = self.biases[st.index]
+        k, n = self.weights[st.index].shape
         if x.shape[-1] != k:
             raise ValueError(f"layer {st.first} expects {k} inputs per row, got {x.shape[-1]}")
         lead = x.shape[:-1]
@@ -82,6 +119,19 @@ class FusedPredictor:
         out = torch.empty(rows, n, device=self.dev, dtype=torch.float32 if last else self.compute)
         if rows == 0:
             return out.view(*lead, n)
+        if fp8 and rows < SKINNY_BELOW:
+            w8, scale = self._quantised(st.index)
+            ok8 = self._w8_ok.get(st.index)
+            if ok8 is None:  # a property of the layer, as _skinny_ok
+                ok8 = self._w8_ok[st.index] = PF.gemm_skinny_w8_eligible(x2[:PF.SKINNY_MAX_ROWS], w8, scale,
+                                                                          out[:PF.SKINNY_MAX_ROWS])
+            if ok8:
+                for r0 in range(0, rows, PF.SKINNY_MAX_ROWS):
+                    PF.gemm_skinny_w8(x2[r0:r0 + PF.SKINNY_MAX_ROWS], w8, scale, out[r0:r0 + PF.SKINNY_MAX_ROWS],
+                                      bias=bias, act=st.act)
+                return out.view(*lead, n)
+        # the bf16 / fp32 kernels: on the default copies, or on the dequantised ones of an fp8 request
+        w = self._dequantised(st.index) if fp8 else self.weights[st.index]
         if rows < SKINNY_BELOW:
             ok = self._skinny_ok.get(st.index)
             for r0 in range(0, rows, PF.SKINNY_MAX_ROWS):
@@ -131,9 +181,16 @@ class FusedPredictor:
         return out
 
     @torch.no_grad()
-    def forward(self, x: Tensor) -> Tensor:
+    def forward(self, x: Tensor, weights: str | None = None) -> Tensor:
         """``x``: what ``_forward`` takes — a vector, a batch, or id sequences for embedding models
-        (any float / int dtype; moved to the model's device). Returns the fp32 output tensor."""
+        (any float / int dtype; moved to the model's device). Returns the fp32 output tensor.
+        ``weights="fp8"``: the linear stages read the e4m3 weight copies (module docstring)."""
+        if weights not in (None, "fp8"):
+            raise ValueError(f"unknown weights {weights!r}: None (the model's own precision) or 'fp8'")
+        fp8 = weights == "fp8"
+        if fp8 and self.compute != torch.bfloat16:
+            raise ValueError(f"weights='fp8' is for bfloat16 / fp8 models; a {self.model.precision.name} model "
+                             "asked for exact weights")
         x = x.to(self.dev)
         if self.stages[0].kind != "embed" and x.dtype != self.compute:
             x = x.to(self.compute)
@@ -144,7 +201,7 @@ class FusedPredictor:
                 x = st.layer.forward(x)  # a view
             elif st.kind == "gemm":
                 vector = x.dim() == 1
-                x = self._linear(st, x.unsqueeze(0) if vector else x)
+                x = self._linear(st, x.unsqueeze(0) if vector else x, fp8)
                 x = x.squeeze(0) if vector else x
             else:
                 x = self._batchnorm(st, x)

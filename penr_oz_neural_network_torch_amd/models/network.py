@@ -290,7 +290,7 @@ class NeuralNetworkModel(MultiLayerPerceptron):
             out = out.float()
         return out.tolist(), cost.item() if cost.numel() > 0 else None
 
-    def predict(self, input_data: list) -> list:
+    def predict(self, input_data: list, weights: str | None = None) -> list:
         """Outputs only, forward-only: what ``compute_output(input_data)[0]`` returns, without a
         cost or a target, layers in eval mode, nothing recorded for autograd.
 
@@ -300,14 +300,29 @@ class NeuralNetworkModel(MultiLayerPerceptron):
         have changed (``train``, ``set_model_data``, re-placement), so it never serves stale
         weights. Models it cannot schedule (``float64``, unusual layer orders), CPU models and the
         reference runtime run the layer loop under ``no_grad`` — there the result is bit-identical
-        to ``compute_output``'s."""
+        to ``compute_output``'s.
+
+        ``weights="fp8"`` opts into weight-only quantised inference: the linear layers read OCP
+        e4m3 copies of the weights with one power-of-two scale per output column (activations stay
+        bf16, accumulation fp32; see :mod:`..engine.predictor`). Only GPU models whose compute
+        dtype is bf16 (``bfloat16`` / ``fp8``) and which the fused predictor can schedule take it;
+        anything else raises ``ValueError`` — there is no silent fall-back to unquantised weights.
+        ``None`` is the model's own precision."""
+        if weights is not None:
+            if weights != "fp8":
+                raise ValueError(f"unknown weights {weights!r}: None (the model's own precision) or 'fp8'")
+            if not self.on_gpu:
+                raise ValueError("weights='fp8' needs a model on a GPU (the e4m3 kernels are HIP kernels)")
         x = self._input_tensor(input_data)
         with torch.no_grad():
             predictor = self._fused_predictor() if self.on_gpu else None
+            if weights is not None and predictor is None:
+                raise ValueError(f"weights='fp8' is not available for model {self.model_id}: "
+                                 f"{getattr(self, '_predictor_reason', 'no fused predictor')}")
             if predictor is not None:
                 for layer in self.layers:
                     layer.training = False
-                out = predictor.forward(x)
+                out = predictor.forward(x, weights=weights) if weights is not None else predictor.forward(x)
             else:
                 out = self._forward(x, None)[0][-1].detach()
                 if out.dtype == torch.bfloat16:
@@ -322,6 +337,7 @@ class NeuralNetworkModel(MultiLayerPerceptron):
             except UnsupportedModel as e:
                 log.info(f"Model {self.model_id}: fused predictor unavailable ({e}); predicting through the layers")
                 self._predictor = False
+                self._predictor_reason = str(e)
         return self._predictor or None
 
     def _forward(self, input_tensor: Tensor, target: list, dropout_rate=0.0) -> Tuple[list[Tensor], Tensor]:

@@ -207,6 +207,92 @@ def gemm_skinny(x: Tensor, w: Tensor, out: Tensor, *, bias: Tensor | None = None
     return out
 
 
+# --------------------------------------------------------------------------------------------
+# weight-only e4m3 inference: column quantiser and its skinny GEMM
+# --------------------------------------------------------------------------------------------
+E4M3_MAX = 448.0
+
+
+def _check_quantisable(w: Tensor) -> None:
+    if w.dim() != 2 or w.dtype != torch.float32:
+        raise ValueError(f"quantize_cols takes a 2-D float32 [in, out] weight matrix, got {tuple(w.shape)} {w.dtype}")
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("quantize_cols: the weight matrix holds a non-finite value; nothing was quantised")
+
+
+def quantize_cols_reference(w: Tensor) -> tuple[Tensor, Tensor]:
+    """Pure-torch definition of :func:`quantize_cols` (runs on the CPU): ``w [K, N]`` fp32 ->
+    ``(w8, scale)`` with ``w8`` a ``float8_e4m3fn`` ``[K, N]`` tensor and ``scale [N]`` fp32 powers of two.
+
+    Per column, ``amax = max_k |w[k, n]| = m * 2^x`` with ``m`` in ``[0.5, 1)`` (frexp);
+    ``e = x - 9`` if ``m <= 0.875`` else ``x - 8`` — the smallest ``e`` with ``amax <= 448 * 2^e`` —
+    but not below -126 (the scale stays a normal fp32; only ``amax < 2^-118`` meets that floor);
+    ``scale = 2^e``, 1 for an all-zero column; ``w8 = e4m3_rne(clamp(w * 2^-e, -448, 448))``.
+    The multiply is exact, so ``w8.float() * scale`` is exactly representable in bf16."""
+    _check_quantisable(w)
+    amax = w.abs().amax(dim=0) if w.shape[0] else torch.zeros(w.shape[1], dtype=torch.float32, device=w.device)
+    m, x = torch.frexp(amax)
+    e = (x - 9 + (m > 0.875).to(x.dtype)).clamp(min=-126)
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    one = torch.ones_like(amax)
+    scale = torch.ldexp(one, e)
+    w8 = (w * torch.ldexp(one, -e)).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+    return w8, scale
+
+
+def quantize_cols(w: Tensor) -> tuple[Tensor, Tensor]:
+    """``w [K, N]`` fp32 on the GPU (unit inner stride, any row stride) -> ``(w8, scale)`` exactly as
+    :func:`quantize_cols_reference` defines them, by the two-phase kernel of csrc/quant_cols.hip.
+    ``w8`` is a contiguous ``float8_e4m3fn`` tensor in ``w``'s ``[in, out]`` layout. A non-finite
+    weight raises ``ValueError`` (one ``isfinite`` check on the host side); nothing is quantised."""
+    if not w.is_cuda:
+        raise ValueError("quantize_cols takes a GPU tensor (quantize_cols_reference runs on the CPU)")
+    _check_quantisable(w)
+    ops = _ops()
+    if w.shape[1] > 1 and w.stride(1) != 1:
+        w = w.contiguous()
+    k, n = w.shape
+    w8 = torch.empty(k, n, device=w.device, dtype=torch.float8_e4m3fn)
+    scale = torch.ones(n, device=w.device, dtype=torch.float32)
+    if k and n:
+        ops.quantize_cols(w, w8, scale, torch.zeros(n, device=w.device, dtype=torch.float32))
+    return w8, scale
+
+
+def dequantize_cols(w8: Tensor, scale: Tensor, dtype: torch.dtype = torch.bfloat16) -> Tensor:
+    """``w8.float() * scale`` — exact in fp32 and, the scales being powers of two, in bf16."""
+    return (w8.float() * scale).to(dtype)
+
+
+def gemm_skinny_w8_eligible(x: Tensor, w8: Tensor, scale: Tensor, out: Tensor) -> bool:
+    """Whether :func:`gemm_skinny_w8` takes these operands: GPU tensors, bf16 ``x [M, K]``,
+    ``float8_e4m3fn`` ``w8 [K, N]``, fp32 ``scale [N]``, ``1 <= M <= 16``, ``out [M, N]`` bf16 / fp32,
+    unit inner strides, ``w8``'s row bytes (= N) and leading dimension multiples of 16 and its base
+    16-B aligned."""
+    if not (x.is_cuda and w8.is_cuda and scale.is_cuda and out.is_cuda) or x.dim() != 2 or w8.dim() != 2 or out.dim() != 2:
+        return False
+    if w8.dtype != torch.float8_e4m3fn or x.shape[1] != w8.shape[0] or out.shape != (x.shape[0], w8.shape[1]):
+        return False
+    if scale.dtype != torch.float32 or scale.dim() != 1 or scale.shape[0] != w8.shape[1] or not scale.is_contiguous():
+        return False
+    return bool(_ops().gemm_skinny_w8_eligible(x, w8, scale, out))
+
+
+def gemm_skinny_w8(x: Tensor, w8: Tensor, scale: Tensor, out: Tensor, *, bias: Tensor | None = None,
+                   act: int = ACT_NONE) -> Tensor:
+    """``out[M,N] = act(scale[n] * (x[M,K] @ w8[K,N]) + bias[n])`` for ``1 <= M <= 16``: the weight-only
+    quantised sibling of :func:`gemm_skinny` (csrc/gemm_skinny_w8.hip). ``x`` bf16, ``w8`` a
+    ``torch.float8_e4m3fn`` tensor in the ``[in, out]`` layout with one power-of-two ``scale`` per
+    column (:func:`quantize_cols`), fp32 ``bias``, fp32 accumulation in a fixed order
+    (bit-reproducible; a row's result does not depend on the rows sent with it). Products and the
+    scale multiply are exact, so this computes ``gemm_skinny`` on the dequantised bf16 matrix up to
+    summation order. A ``scale`` / ``bias`` whose length is not N, or a ``w8`` of another dtype, is a
+    structural error; operands that are not :func:`gemm_skinny_w8_eligible` raise; nothing is
+    launched for either."""
+    _ops().gemm_skinny_w8(x, w8, scale, out, bias, act)
+    return out
+
+
 def _as_2d(x: Tensor) -> tuple[Tensor, tuple]:
     lead = x.shape[:-1]
     return x.reshape(-1, x.shape[-1]).contiguous(), lead
@@ -513,5 +599,6 @@ def tensor_summary(t: Tensor, algo: str | None, bins: int) -> dict:
     return out
 
 
-__all__ = ["gemm", "gemm_path", "gemm_skinny", "gemm_skinny_eligible", "linear", "activation", "dropout", "softmax", "cross_entropy", "mse_loss",
+__all__ = ["gemm", "gemm_path", "gemm_skinny", "gemm_skinny_eligible", "gemm_skinny_w8", "gemm_skinny_w8_eligible",
+           "quantize_cols", "quantize_cols_reference", "dequantize_cols", "linear", "activation", "dropout", "softmax", "cross_entropy", "mse_loss",
            "batchnorm", "embedding", "tensor_summary", "epi_spec", "new_seed"]
