@@ -6,6 +6,7 @@ existing clients, its test-suite and the dashboard work unchanged:
     GET  /              -> 307 /dashboard            GET /dashboard      -> HTML page
     POST /model/        create + serialize            POST /output/       inference (+ cost)
     POST /predict/      batch inference, outputs only (models stay loaded between requests)
+    POST /generate/     token sampling from a next-token model (same loaded models as /predict/)
     PUT  /train/        202, training in background   (409 while that model is training)
     GET  /progress/     progress / avg cost / status  GET /stats/         training diagnostics
     DELETE /model/      204
@@ -121,6 +122,19 @@ class PredictRequest(ModelRequest):
                                 description="Weight format to predict from. Omitted: the model's own precision. 'fp8': "
                                             "weight-only e4m3 copies, one power-of-two scale per output column (GPU "
                                             "models with dtype bfloat16 or fp8; anything else answers 400)")
+
+
+class GenerateRequest(ModelRequest):
+    context: list = Field(..., description="One id list or a batch of id lists. A row shorter than the model's context "
+                                           "length is left-padded with pad_token; of a longer one the last ids count.")
+    max_new_tokens: int = Field(..., description="Tokens to sample per row (1 to 4096).")
+    temperature: float = Field(1.0, description="Softmax temperature; 0 is greedy (the most likely token).")
+    top_k: int | None = Field(None, description="Sample among the k most likely tokens only (ties at the k-th stay).")
+    seed: int | None = Field(None, description="64-bit seed naming the random draws; omitted: drawn by the server "
+                                               "and returned, so the call can be repeated.")
+    stop_token: int | None = Field(None, description="A row ends with its first occurrence of this id (inclusive).")
+    pad_token: int = Field(0, description="Id that left-pads short context rows.")
+    weights: str | None = Field(None, description="'fp8': weight-only e4m3 copies, as on /predict/.")
 
 
 class TrainingRequest(ModelRequest):
@@ -277,6 +291,29 @@ def predict_model_output(body: PredictRequest = Body(..., openapi_examples=PREDI
             return {"output_vectors": model.predict(body.inputs)}
         return {"output_vectors": model.predict(body.inputs, weights=body.weights)}
     except IndexError as e:  # an embedding id outside the vocabulary is a bad request
+        raise ValueError(str(e))
+
+
+GENERATE_EXAMPLES = {
+    "single": {"summary": "One context", "description": "Ten tokens after one context of a character model "
+                                                        "(vocabulary 27, id 0 ends a word).",
+               "value": {"model_id": "names", "context": [0, 0, 5], "max_new_tokens": 10, "stop_token": 0}},
+    "batch": {"summary": "A batch, reproducible", "description": "Two rows of different lengths (the short one is "
+                                                                  "left-padded), top-k sampling with a fixed seed.",
+              "value": {"model_id": "names", "context": [[13], [1, 14, 14, 1]], "max_new_tokens": 8, "temperature": 0.8,
+                        "top_k": 5, "seed": 1234, "stop_token": 0}},
+}
+
+
+@app.post("/generate/")
+def generate_tokens(body: GenerateRequest = Body(..., openapi_examples=GENERATE_EXAMPLES)):
+    model_id = body.model_id
+    log.info(f"Requesting generation for model {model_id}")
+    model = _cached_model(model_id)
+    try:
+        return model.generate(body.context, body.max_new_tokens, temperature=body.temperature, top_k=body.top_k,
+                              seed=body.seed, stop_token=body.stop_token, pad_token=body.pad_token, weights=body.weights)
+    except IndexError as e:  # a context id outside the vocabulary is a bad request
         raise ValueError(str(e))
 
 

@@ -681,6 +681,40 @@ void softmax_rows_op(const Tensor& x, const Tensor& y) {
   PZ_HIP_CHECK(pz::softmax_rows(x.data_ptr(), y.data_ptr(), dt_of(x), rows, cols, cur_stream(x)));
 }
 
+// one token per row into seq[:, pos] (csrc/sample.hip); `key` = layer_key(seed, step) of the host
+void sample_rows_op(const Tensor& logits, const Tensor& seq, const Tensor& done, int64_t pos, double temperature,
+                    int64_t top_k, int64_t key, int64_t stop_token, int64_t row0) {
+  check_dev(logits, "logits");
+  check_dev(seq, "seq");
+  check_dev(done, "done");
+  TORCH_CHECK(logits.scalar_type() == at::kFloat && logits.dim() == 2 && logits.is_contiguous(),
+              "pz::sample_rows: logits must be a contiguous fp32 [rows, V] tensor");
+  TORCH_CHECK(seq.scalar_type() == at::kLong && seq.dim() == 2 && seq.is_contiguous(),
+              "pz::sample_rows: seq must be a contiguous int64 [rows, length] tensor");
+  TORCH_CHECK(done.scalar_type() == at::kInt && done.dim() == 1 && done.is_contiguous(),
+              "pz::sample_rows: done must be a contiguous int32 [rows] tensor");
+  const int64_t rows = logits.size(0), cols = logits.size(1);
+  TORCH_CHECK(seq.size(0) == rows && done.size(0) == rows, "pz::sample_rows: logits, seq and done must have the same rows");
+  TORCH_CHECK(cols >= 1 && cols <= pz::kSampleMaxCols && rows <= INT32_MAX, "pz::sample_rows: shape out of range");
+  TORCH_CHECK(pos >= 0 && pos < seq.size(1), "pz::sample_rows: pos ", pos, " is outside seq of length ", seq.size(1));
+  TORCH_CHECK(temperature >= 0.0, "pz::sample_rows: temperature must be >= 0 and not NaN, got ", temperature);
+  TORCH_CHECK(top_k >= 0, "pz::sample_rows: top_k must be >= 0 (0 = off)");
+  pz::SampleArgs a{};
+  a.logits = logits.data_ptr<float>();
+  a.rows = static_cast<int>(rows);
+  a.cols = static_cast<int>(cols);
+  a.seq = seq.data_ptr<int64_t>();
+  a.seq_ld = seq.size(1);
+  a.pos = pos;
+  a.done = done.data_ptr<int>();
+  a.temperature = static_cast<float>(temperature);
+  a.top_k = static_cast<int>(std::min<int64_t>(top_k, cols));
+  a.key = static_cast<uint32_t>(key);
+  a.row0 = static_cast<uint32_t>(row0);
+  a.stop_token = stop_token;
+  PZ_HIP_CHECK(pz::sample_rows(a, cur_stream(logits)));
+}
+
 void softmax_bwd_op(const Tensor& g, const Tensor& y, const Tensor& dx) {
   check_dev(g, "g");
   TORCH_CHECK(g.is_contiguous() && y.is_contiguous() && dx.is_contiguous(), "pz::softmax_bwd");
@@ -1181,6 +1215,8 @@ TORCH_LIBRARY(pz, m) {
   m.def("mse_head(Tensor y, Tensor target, int rows_valid, Tensor(a!)? loss, float loss_scale, Tensor(b!)? dh, "
         "float grad_scale, Tensor(c!)? colsum, int[] epi_i, float[] epi_f, int idx_ld) -> ()");
   m.def("softmax_rows(Tensor x, Tensor(a!) y) -> ()");
+  m.def("sample_rows(Tensor logits, Tensor(a!) seq, Tensor(b!) done, int pos, float temperature, int top_k, int key, "
+        "int stop_token=-1, int row0=0) -> ()");
   m.def("softmax_bwd(Tensor g, Tensor y, Tensor(a!) dx) -> ()");
   m.def("colsum(Tensor x, Tensor(a!) out) -> ()");
   m.def("gather_rows(Tensor data, Tensor? indices, int seed_lo, int seed_hi, Tensor(a!) out, int rows_valid, "
@@ -1237,6 +1273,7 @@ TORCH_LIBRARY_IMPL(pz, CUDA, m) {
 
   m.impl("mse_head", TORCH_FN(mse_head_op));
   m.impl("softmax_rows", TORCH_FN(softmax_rows_op));
+  m.impl("sample_rows", TORCH_FN(sample_rows_op));
   m.impl("softmax_bwd", TORCH_FN(softmax_bwd_op));
   m.impl("colsum", TORCH_FN(colsum_op));
   m.impl("gather_rows", TORCH_FN(gather_rows_op));

@@ -106,6 +106,21 @@ hipError_t xent_head(const XentArgs& a, hipStream_t s);
 hipError_t mse_head(const MseArgs& a, hipStream_t s);
 hipError_t softmax_rows(const void* x, void* y, int dtype, int rows, int cols, hipStream_t s);
 hipError_t softmax_bwd(const void* g, const void* y, void* dx, int dtype, int rows, int cols, hipStream_t s);
+// one token per row of fp32 logits: greedy / temperature / top-k, counter-based uniform (sample.hip)
+constexpr int kSampleMaxCols = 1 << 30;
+struct SampleArgs {
+  const float* logits;  // [rows][cols]
+  int rows, cols;
+  int64_t* seq;         // [rows][seq_ld]; the token of row r goes to seq[r][pos]
+  int64_t seq_ld, pos;
+  int* done;            // [rows]: set when a row draws stop_token; a set row writes stop_token
+  float temperature;    // 0 = greedy
+  int top_k;            // 0 = off
+  uint32_t key;         // u = (mix32((row0 + r) ^ key) >> 8) * 2^-24
+  uint32_t row0;
+  int64_t stop_token;   // -1 = none
+};
+hipError_t sample_rows(const SampleArgs& a, hipStream_t s);
 // column sums, out[c] += sum_r x[r][c]; ws (colsum_parts(rows) x cols accumulators of out's dtype):
 // deterministic ordered fold instead of float atomics
 constexpr int kColsumRows = 256;

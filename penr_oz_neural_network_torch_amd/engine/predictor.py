@@ -46,6 +46,15 @@ of the eligible layers. Measured (profiles/predict_w8_latency.txt): the e4m3 ker
 one at 1 row on every layer shape tried and at every row count on an 8192 x 8192 layer, and is
 1.2-1.4x slower at 16 rows on layers of 16 Mi weights or fewer; the chunks still go through it, so
 that the memory held does not depend on the batch sizes a process happens to see.
+
+Token generation, :meth:`FusedPredictor.generate` (embedding first, softmax head, at least as many
+embedding rows as classes): the context ``[rows, L]`` (``L`` = :attr:`FusedPredictor.context_length`,
+the product of the flatten ratios) is uploaded once into an int64 buffer ``seq [rows, L + steps]``
+and range-checked once; step ``s`` runs the stage loop above without the head (``_logits``) on the
+window ``seq[:, s : s + L]`` — nothing is shifted in place, ``embedding_fwd`` reads a contiguous copy
+of the view, its id check is skipped because the ids come from the sampling kernel — and one
+``PF.sample_rows`` launch (csrc/sample.hip) draws ``seq[:, L + s]`` from the fp32 logits. No host
+read happens inside the loop; the caller downloads ``seq[:, L:]`` once.
 """
 from __future__ import annotations
 
@@ -171,32 +180,33 @@ class FusedPredictor:
                                    ws[:cols], ws[cols:2 * cols], ws[2 * cols:], ei, ef, 0)
         return y
 
-    def _embed(self, st, ids: Tensor) -> Tensor:
+    def _embed(self, st, ids: Tensor, check: bool = True) -> Tensor:
         table = self.store.view(st.seg_w)
         vocab = table.shape[0]
-        PF.check_index_range(ids.reshape(-1), -vocab, vocab, "index", vocab)  # as PF.embedding
+        if check:  # (one device sync; the generation loop's ids come from the sampling kernel and are < V)
+            PF.check_index_range(ids.reshape(-1), -vocab, vocab, "index", vocab)  # as PF.embedding
         idc = ids.contiguous()
         out = torch.empty(*idc.shape, table.shape[1], device=self.dev, dtype=self.compute)
         torch.ops.pz.embedding_fwd(table, idc, out)
         return out
 
-    @torch.no_grad()
-    def forward(self, x: Tensor, weights: str | None = None) -> Tensor:
-        """``x``: what ``_forward`` takes — a vector, a batch, or id sequences for embedding models
-        (any float / int dtype; moved to the model's device). Returns the fp32 output tensor.
-        ``weights="fp8"``: the linear stages read the e4m3 weight copies (module docstring)."""
+    def _want_fp8(self, weights: str | None) -> bool:
         if weights not in (None, "fp8"):
             raise ValueError(f"unknown weights {weights!r}: None (the model's own precision) or 'fp8'")
         fp8 = weights == "fp8"
         if fp8 and self.compute != torch.bfloat16:
             raise ValueError(f"weights='fp8' is for bfloat16 / fp8 models; a {self.model.precision.name} model "
                              "asked for exact weights")
+        return fp8
+
+    def _logits(self, x: Tensor, fp8: bool = False, check_ids: bool = True) -> Tensor:
+        """The stage loop without the head: the fp32 output of the last stage (a softmax head's logits)."""
         x = x.to(self.dev)
         if self.stages[0].kind != "embed" and x.dtype != self.compute:
             x = x.to(self.compute)
         for st in self.stages:
             if st.kind == "embed":
-                x = self._embed(st, x)
+                x = self._embed(st, x, check_ids)
             elif st.kind == "flatten":
                 x = st.layer.forward(x)  # a view
             elif st.kind == "gemm":
@@ -207,6 +217,14 @@ class FusedPredictor:
                 x = self._batchnorm(st, x)
         if x.dtype != torch.float32:
             x = x.float()
+        return x
+
+    @torch.no_grad()
+    def forward(self, x: Tensor, weights: str | None = None) -> Tensor:
+        """``x``: what ``_forward`` takes — a vector, a batch, or id sequences for embedding models
+        (any float / int dtype; moved to the model's device). Returns the fp32 output tensor.
+        ``weights="fp8"``: the linear stages read the e4m3 weight copies (module docstring)."""
+        x = self._logits(x, self._want_fp8(weights))
         if self.head == "softmax":
             xc = x.contiguous()
             y = torch.empty_like(xc)
@@ -214,6 +232,63 @@ class FusedPredictor:
                 torch.ops.pz.softmax_rows(xc, y)
             x = y
         return x
+
+    # ------------------------------------------------------------------------------------
+    # token generation
+    # ------------------------------------------------------------------------------------
+    @property
+    def context_length(self) -> int:
+        """Ids per row for which the model's output is one distribution per row: the product of the
+        flatten ratios (each flatten merges that many adjacent positions)."""
+        length = 1
+        for st in self.stages:
+            if st.kind == "flatten":
+                length *= int(st.layer.ratio)
+        return length
+
+    def generation_unsupported(self) -> str | None:
+        """Why this model cannot generate tokens (None: it can)."""
+        if self.stages[0].kind != "embed":
+            return "token generation needs an embedding first layer"
+        if self.head != "softmax":
+            return "token generation needs a softmax head"
+        vocab, width = self.store.view(self.stages[0].seg_w).shape[0], self.stages[-1].out_width
+        if width > vocab:
+            return f"the model predicts {width} classes but embeds {vocab} ids: a sampled id could not be fed back"
+        return None
+
+    @torch.no_grad()
+    def generate(self, context: Tensor, max_new_tokens: int, temperature: float = 1.0, top_k: int | None = None,
+                 seed: tuple[int, int] = (0, 0), stop_token: int | None = None, weights: str | None = None) -> Tensor:
+        """``context``: int ids ``[rows, context_length]``. Returns the int64 ``[rows, max_new_tokens]``
+        continuation, on the device. One upload, then per token the forward kernels on the window
+        ``seq[:, s : s + L]`` and one ``PF.sample_rows`` launch that writes ``seq[:, L + s]``; nothing is
+        read back inside the loop. Step ``s`` of row ``r`` draws ``PF.sample_uniform(seed, r, s)``; a row
+        that drew ``stop_token`` repeats it from then on."""
+        fp8 = self._want_fp8(weights)
+        reason = self.generation_unsupported()
+        if reason is not None:
+            raise ValueError(reason)
+        length, steps = self.context_length, int(max_new_tokens)
+        context = torch.as_tensor(context)
+        if context.dim() != 2 or context.shape[1] != length or context.is_floating_point():
+            raise ValueError(f"context must be an int tensor [rows, {length}], got {tuple(context.shape)} {context.dtype}")
+        if steps < 1:
+            raise ValueError(f"max_new_tokens must be >= 1, got {max_new_tokens}")
+        rows = context.shape[0]
+        seq = torch.empty(rows, length + steps, device=self.dev, dtype=torch.int64)
+        seq[:, :length] = context.to(device=self.dev, dtype=torch.int64)
+        if rows == 0:
+            return seq[:, length:]
+        vocab = self.store.view(self.stages[0].seg_w).shape[0]
+        PF.check_index_range(seq[:, :length].reshape(-1), -vocab, vocab, "index", vocab)  # once; the loop skips it
+        done = torch.zeros(rows, device=self.dev, dtype=torch.int32)
+        width = self.stages[-1].out_width
+        for s in range(steps):
+            logits = self._logits(seq[:, s:s + length], fp8, check_ids=False).reshape(rows, width)
+            PF.sample_rows(logits, seq, done, length + s, seed=seed, step=s, temperature=temperature, top_k=top_k,
+                           stop_token=stop_token)
+        return seq[:, length:]
 
 
 __all__ = ["FusedPredictor", "UnsupportedModel", "SKINNY_BELOW"]

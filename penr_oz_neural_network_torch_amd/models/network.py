@@ -340,6 +340,120 @@ class NeuralNetworkModel(MultiLayerPerceptron):
                 self._predictor_reason = str(e)
         return self._predictor or None
 
+    # ------------------------------------------------------------------------------------
+    # token generation
+    # ------------------------------------------------------------------------------------
+    @property
+    def context_length(self) -> int:
+        """Ids per row of a next-token model (embedding -> flatten ... -> softmax): the product of
+        the flatten ratios."""
+        length = 1
+        for layer in self.layers:
+            if layer.algo == "flatten":
+                length *= int(layer.ratio)
+        return length
+
+    def _generation_shape(self) -> tuple[int, int]:
+        """(embedding rows, output classes) of a model that can generate; ValueError with the reason."""
+        if not self.algos or self.algos[0] != "embedding" or self.layers[0].weights is None:
+            raise ValueError(f"model {self.model_id} cannot generate: token generation needs an embedding first layer")
+        if self.algos[-1] != "softmax":
+            raise ValueError(f"model {self.model_id} cannot generate: token generation needs a softmax head")
+        widths = [layer.weights.shape[1] for layer in self.layers[1:] if layer.algo == "linear" and layer.weights is not None]
+        if not widths:
+            raise ValueError(f"model {self.model_id} cannot generate: no linear layer produces the logits")
+        vocab, classes = int(self.layers[0].weights.shape[0]), int(widths[-1])
+        if classes > vocab:
+            raise ValueError(f"model {self.model_id} cannot generate: it predicts {classes} classes but embeds {vocab} "
+                             "ids, so a sampled id could not be fed back")
+        return vocab, classes
+
+    def generate(self, context: list, max_new_tokens: int, temperature: float = 1.0, top_k: int | None = None,
+                 seed: int | None = None, stop_token: int | None = None, pad_token: int = 0,
+                 weights: str | None = None) -> dict:
+        """Sample ``max_new_tokens`` ids after ``context`` from a next-token model (embedding first,
+        softmax head): ``{"tokens": [[...], ...], "seed": int}``, one row per context row.
+
+        ``context`` is one id list or a batch of lists; a row shorter than :attr:`context_length`
+        is left-padded with ``pad_token``, a longer one contributes its last ``context_length`` ids.
+        Each step feeds the last ``context_length`` ids, takes the logits and draws by the rule of
+        :func:`..ops.functional.sample_rows_reference`: ``temperature == 0`` is greedy, ``top_k``
+        keeps the k largest logits (ties included), and row ``r`` draws
+        ``PF.sample_uniform((seed & 0xFFFFFFFF, seed >> 32), r, step)`` at step ``step`` — so a seed
+        names its output; ``seed=None`` takes 64 bits from ``os.urandom`` and returns them. A row is
+        cut after its first ``stop_token`` (inclusive).
+
+        GPU models with a fused predictor keep the whole loop on the device
+        (:meth:`..engine.predictor.FusedPredictor.generate`: the forward kernels plus one sampling
+        launch per token, one download at the end). CPU models, the reference runtime and models
+        without a predictor run the layer loop under ``no_grad`` with the same rule and the same
+        random numbers. ``weights="fp8"`` as in :meth:`predict`."""
+        from ..ops import functional as PF
+        if weights is not None:
+            if weights != "fp8":
+                raise ValueError(f"unknown weights {weights!r}: None (the model's own precision) or 'fp8'")
+            if not self.on_gpu:
+                raise ValueError("weights='fp8' needs a model on a GPU (the e4m3 kernels are HIP kernels)")
+        vocab, classes = self._generation_shape()
+        if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or not 1 <= max_new_tokens <= 4096:
+            raise ValueError(f"max_new_tokens must be an integer in [1, 4096], got {max_new_tokens!r}")
+        if not isinstance(temperature, (int, float)) or temperature != temperature or temperature < 0:
+            raise ValueError(f"temperature must be >= 0, got {temperature!r}")
+        if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 1):
+            raise ValueError(f"top_k must be an integer >= 1, got {top_k!r}")
+        if stop_token is not None and (not isinstance(stop_token, int) or not 0 <= stop_token < classes):
+            raise ValueError(f"stop_token {stop_token!r} is outside the vocabulary of {classes}")
+        if not isinstance(pad_token, int) or not 0 <= pad_token < vocab:
+            raise ValueError(f"pad_token {pad_token!r} is outside the vocabulary of {vocab}")
+        if seed is None:
+            import os
+            seed = int.from_bytes(os.urandom(8), "little")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+            raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+        key = (seed & 0xFFFFFFFF, seed >> 32)
+        if not isinstance(context, list) or not context:
+            raise ValueError("context must be a non-empty id list or a non-empty batch of id lists")
+        batch = context if isinstance(context[0], list) else [context]
+        length = self.context_length
+        window = []
+        for row in batch:
+            if not isinstance(row, list) or any(isinstance(v, bool) or not isinstance(v, int) for v in row):
+                raise ValueError("context rows must be lists of integer ids")
+            row = row[-length:]
+            window.append([pad_token] * (length - len(row)) + row)
+        ids = torch.tensor(window, dtype=torch.int64)
+        PF.check_index_range(ids.reshape(-1), -vocab, vocab, "index", vocab)  # IndexError, as predict
+        with torch.no_grad():
+            predictor = self._fused_predictor() if self.on_gpu else None
+            if weights is not None and predictor is None:
+                raise ValueError(f"weights='fp8' is not available for model {self.model_id}: "
+                                 f"{getattr(self, '_predictor_reason', 'no fused predictor')}")
+            for layer in self.layers:
+                layer.training = False
+            if predictor is not None:
+                tokens = predictor.generate(ids, max_new_tokens, temperature=float(temperature), top_k=top_k, seed=key,
+                                            stop_token=stop_token, weights=weights).tolist()
+            else:
+                tokens = self._generate_layers(ids, max_new_tokens, float(temperature), top_k, key, stop_token)
+        if stop_token is not None:
+            tokens = [row[:row.index(stop_token) + 1] if stop_token in row else row for row in tokens]
+        return {"tokens": tokens, "seed": seed}
+
+    def _generate_layers(self, ids: Tensor, steps: int, temperature: float, top_k, key, stop_token) -> list:
+        """The generation loop through the layers (``_forward`` in eval mode) with the pure-torch sampler."""
+        from ..ops import functional as PF
+        rows, length = ids.shape
+        seq = torch.cat([ids, torch.zeros(rows, steps, dtype=torch.int64)], dim=1).to(self.device)
+        done = torch.zeros(rows, dtype=torch.bool, device=self.device)
+        for s in range(steps):
+            logits = self._forward(seq[:, s:s + length], None)[0][-2].detach()  # the softmax layer's input
+            token = PF.sample_rows_reference(logits.reshape(rows, -1), key, s, temperature, top_k)
+            if stop_token is not None:
+                token = torch.where(done, torch.full_like(token, stop_token), token)
+                done |= token == stop_token
+            seq[:, length + s] = token
+        return seq[:, length:].tolist()
+
     def _forward(self, input_tensor: Tensor, target: list, dropout_rate=0.0) -> Tuple[list[Tensor], Tensor]:
         target_specified = target is not None and (isinstance(target, Tensor) or all(t is not None for t in target))
         gpu = self.on_gpu

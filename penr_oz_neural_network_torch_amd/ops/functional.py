@@ -404,6 +404,74 @@ def softmax(x: Tensor) -> Tensor:
     return _Softmax.apply(x)
 
 
+# --------------------------------------------------------------------------------------------
+# token sampling (csrc/sample.hip)
+# --------------------------------------------------------------------------------------------
+def sample_uniform(seed: tuple[int, int], row: int, step: int) -> float:
+    """The uniform in ``[0, 1)`` that row ``row`` draws at generation step ``step``: 24 bits of
+    ``mix32(row ^ layer_key(seed, step))`` — integer arithmetic, so exactly the kernel's value."""
+    return (mix32((row & _M32) ^ layer_key(seed, step)) >> 8) * 2.0 ** -24
+
+
+def _sample_uniforms(seed: tuple[int, int], rows: int, step: int, row0: int, device) -> Tensor:
+    """:func:`sample_uniform` of rows ``row0 .. row0 + rows - 1`` as an fp64 tensor (the same integers)."""
+    x = ((torch.arange(rows, dtype=torch.int64, device=device) + row0) & _M32) ^ layer_key(seed, step)
+    x = x ^ (x >> 16)
+    x = (x * 0x7FEB352D) & _M32
+    x = x ^ (x >> 15)
+    x = (x * 0x846CA68B) & _M32  # (wraps int64; the low 32 bits of the product are exact)
+    x = x ^ (x >> 16)
+    return (x >> 8).double() * 2.0 ** -24
+
+
+def sample_rows_reference(logits: Tensor, seed: tuple[int, int], step: int, temperature: float = 1.0,
+                          top_k: int | None = None, row0: int = 0) -> Tensor:
+    """The sampling rule of :func:`sample_rows` in pure torch, in fp64, on CPU or GPU tensors:
+    ``logits [rows, V]`` (or ``[V]``) -> int64 tokens ``[rows]``. It is the sampler of the runtimes
+    without the kernel and the yardstick of the kernel's tests.
+
+    * top-k: keep the columns whose logit is ``>=`` the k-th largest of the row (ties all stay);
+      ``None`` / ``0`` / ``k >= V`` keep everything;
+    * ``temperature == 0``: the lowest index among the maxima, nothing drawn;
+    * otherwise ``w_c = exp((l_c - max) / T)`` on kept columns (``T`` rounded to fp32, as the kernel
+      receives it), ``u = sample_uniform(seed, row0 + row, step)``, and the token is the smallest
+      kept ``c`` whose inclusive prefix sum of ``w`` exceeds ``u * sum(w)`` — the last kept column if
+      rounding leaves none."""
+    if temperature != temperature or temperature < 0:
+        raise ValueError(f"temperature must be >= 0, got {temperature}")
+    if top_k is not None and top_k < 0:
+        raise ValueError(f"top_k must be >= 0, got {top_k}")
+    lg = logits.detach()
+    lg = (lg.unsqueeze(0) if lg.dim() == 1 else lg.reshape(-1, lg.shape[-1])).double()
+    rows, v = lg.shape
+    idx = torch.arange(v, device=lg.device).expand(rows, v)
+    mx = lg.max(dim=-1, keepdim=True).values
+    if temperature == 0:
+        return torch.where(lg == mx, idx, v).min(dim=-1).values
+    kept = torch.ones_like(lg, dtype=torch.bool)
+    if top_k and top_k < v:
+        kept = lg >= torch.topk(lg, top_k, dim=-1).values[:, -1:]
+    t32 = float(torch.tensor(temperature, dtype=torch.float32))
+    w = torch.where(kept, torch.exp((lg - mx) / t32), torch.zeros_like(lg))
+    cdf = w.cumsum(dim=-1)
+    target = _sample_uniforms(seed, rows, step, row0, lg.device) * cdf[:, -1]
+    first = torch.where(kept & (cdf > target.unsqueeze(1)), idx, v).min(dim=-1).values
+    last_kept = torch.where(kept, idx, -1).max(dim=-1).values
+    return torch.where(first < v, first, last_kept)
+
+
+def sample_rows(logits: Tensor, seq: Tensor, done: Tensor, pos: int, *, seed: tuple[int, int], step: int,
+                temperature: float = 1.0, top_k: int | None = None, stop_token: int | None = None,
+                row0: int = 0) -> None:
+    """One token per row of the fp32 ``logits [rows, V]`` into ``seq[:, pos]`` (int64 ``[rows, length]``),
+    by the rule of :func:`sample_rows_reference` with ``u = sample_uniform(seed, row0 + row, step)``
+    (csrc/sample.hip; one launch, nothing comes back to the host). ``done`` (int32 ``[rows]``): a row
+    whose flag is set writes ``stop_token``; a row that draws ``stop_token`` sets its flag. The call is
+    bit-reproducible and a row's token does not depend on the rows sent with it."""
+    _ops().sample_rows(logits, seq, done, pos, float(temperature), int(top_k or 0), layer_key(seed, step),
+                       -1 if stop_token is None else int(stop_token), int(row0))
+
+
 def check_index_range(idx: Tensor, lo: int, hi: int, what: str, size: int | None = None) -> None:
     """Raise IndexError (as ATen / Python indexing do) unless every id is in ``[lo, hi)``.
     The HIP kernels never read outside their tables either way, but a bad id must surface as an
@@ -601,4 +669,5 @@ def tensor_summary(t: Tensor, algo: str | None, bins: int) -> dict:
 
 __all__ = ["gemm", "gemm_path", "gemm_skinny", "gemm_skinny_eligible", "gemm_skinny_w8", "gemm_skinny_w8_eligible",
            "quantize_cols", "quantize_cols_reference", "dequantize_cols", "linear", "activation", "dropout", "softmax", "cross_entropy", "mse_loss",
-           "batchnorm", "embedding", "tensor_summary", "epi_spec", "new_seed"]
+           "batchnorm", "embedding", "tensor_summary", "epi_spec", "new_seed", "sample_rows", "sample_rows_reference",
+           "sample_uniform"]
