@@ -85,8 +85,12 @@ def _compile_cmd(src: str, obj: str) -> list:
 
 
 def _object_key(src: str, hdr: str) -> str:
+    # keyed on what is compiled, how and by which compiler, not on where the tree lies: the library
+    # travels with the tree, and a copy of a fresh build at another path is still fresh
     obj = os.path.join(BUILD, os.path.basename(src) + ".o")
-    return _digest([src], hdr + " ".join(_compile_cmd(src, obj)))
+    cmd = _compile_cmd(src, obj)
+    cmd = [cmd[0]] + [c.replace(PKG, ".") for c in cmd[1:]]
+    return _digest([src], hdr + " ".join(cmd))
 
 
 def _compile(src: str, key: str, manifest: dict, force: bool) -> str:

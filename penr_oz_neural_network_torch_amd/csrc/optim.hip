@@ -241,6 +241,16 @@ PZ_DEV void optimizer_block(const OptArgs& args, const OptView<R>& a, int block,
           else
             *reinterpret_cast<float4*>(static_cast<float*>(seg.shadow) + li) = make_float4(p1[0], p1[1], p1[2], p1[3]);
         }
+      } else {  // fp64 masters: the same copies as the scalar loop, element by element
+#pragma unroll
+        for (int k = 0; k < VN; ++k) {
+          const float pf = static_cast<float>(p1[k]);
+          if (seg.w8 != nullptr) seg.w8[li + k] = static_cast<uint8_t>(e4m3x4(pf * q8, 0.f, 0.f, 0.f) & 0xFFu);
+          if (seg.shadow != nullptr) {
+            if (seg.shadow_dtype == DT_BF16) static_cast<uint16_t*>(seg.shadow)[li + k] = f2bf(pf);
+            else static_cast<float*>(seg.shadow)[li + k] = pf;
+          }
+        }
       }
 #pragma unroll
       for (int k = 0; k < VN; ++k) {

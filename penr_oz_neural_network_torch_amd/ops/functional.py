@@ -574,7 +574,7 @@ class _BatchNorm(torch.autograd.Function):
             dx = gc * (gain.to(xc.dtype) * save_inv.to(xc.dtype))
             dgain = (gc * ((xc - save_mean.to(xc.dtype)) * save_inv.to(xc.dtype))).reshape(-1, xc.shape[-1]).sum(0)
             return dx, dgain.to(gain.dtype), gc.reshape(-1, xc.shape[-1]).sum(0).to(bias.dtype), None, None, None, \
-                None, None
+                None, None, None
         dx = torch.empty_like(xc)
         dgain = torch.zeros_like(gain)
         dbias = torch.zeros_like(bias)

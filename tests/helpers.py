@@ -1,5 +1,6 @@
-"""Independent (numpy) re-implementations used as references by the kernel tests."""
+"""Independent (numpy / plain torch) re-implementations used as references by the kernel tests."""
 import numpy as np
+import torch
 
 from penr_oz_neural_network_torch_amd.ops.functional import epoch_key, layer_key
 
@@ -28,3 +29,30 @@ def keep_mask(numel: int, seed_lo: int, seed_hi: int, lid: int, p: float, epoch:
     bits = _mix32((idx >> np.uint64(1)) ^ key)
     r = np.where(idx & np.uint64(1), bits >> np.uint64(16), bits & np.uint64(0xFFFF))
     return r >= np.uint64(thresh)
+
+
+def bit_equal(a: torch.Tensor, b: torch.Tensor) -> bool:
+    """Same shape, dtype and bytes (NaN payloads and the sign of zero included)."""
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    return torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
+
+
+def opt_update_reference(p0, graw, m0, v0, weight, dtype, *, adam, lr, b1, b2, eps, bc1, bc2s, grad_scale, l2):
+    """``opt_update`` (csrc/pz_common.h) evaluated by plain torch in ``dtype``, operation for
+    operation: every hyper-parameter is rounded once to ``dtype`` and ``1 - beta`` is formed in
+    ``dtype``, as the kernel does. ``weight``: bool mask of the elements that take the L2 term.
+    Returns ``(p, m, v)``; SGD returns the moments it was given."""
+    def s(x):
+        return torch.tensor(x, dtype=dtype)
+
+    p0, graw = p0.to(dtype), graw.to(dtype)
+    l2x2 = weight.to(dtype) * (s(2.0) * s(l2))
+    g = graw * s(grad_scale) + l2x2 * p0
+    if not adam:
+        return p0 - s(lr) * g, m0, v0
+    m0, v0 = m0.to(dtype), v0.to(dtype)
+    m = m0 + (s(1.0) - s(b1)) * (g - m0)
+    v = v0 * s(b2) + (s(1.0) - s(b2)) * g * g
+    denom = v.sqrt() / s(bc2s) + s(eps)
+    return p0 - (s(lr) / s(bc1)) * (m / denom), m, v

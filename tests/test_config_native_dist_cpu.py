@@ -60,6 +60,27 @@ def test_native_loader_reports_a_missing_library(monkeypatch, tmp_path):
     assert native.built_sources_stale() is False  # content-hash manifest matches csrc/
 
 
+def test_freshness_key_does_not_depend_on_where_the_tree_lies(monkeypatch, tmp_path):
+    """The library travels with the tree: the same sources, headers and flags in a copy of the
+    tree at another path give the same content key; another compiler does not."""
+    import shutil
+
+    from penr_oz_neural_network_torch_amd import _build
+    here = _build._sources_and_keys()[2]
+    pkg = tmp_path / "elsewhere" / "pkg"
+    shutil.copytree(_build.CSRC, pkg / "csrc")
+    monkeypatch.setattr(_build, "PKG", str(pkg))
+    monkeypatch.setattr(_build, "CSRC", str(pkg / "csrc"))
+    monkeypatch.setattr(_build, "BUILD", str(pkg / "build"))
+    assert _build._sources_and_keys()[2] == here
+    with monkeypatch.context() as m:  # the compiler still counts
+        m.setattr(_build, "_hipcc", lambda: "/some/other/rocm/bin/hipcc")
+        assert _build._sources_and_keys()[2] != here
+    with open(pkg / "csrc" / "optim.hip", "a") as f:  # and so does the content
+        f.write("\n")
+    assert _build._sources_and_keys()[2] != here
+
+
 def test_forced_single_rank_context_over_gloo():
     code = textwrap.dedent("""
         import os, torch
