@@ -56,6 +56,27 @@ T* ptr_or_null(const optional<Tensor>& t) {
   return t.has_value() && t->defined() ? static_cast<T*>(t->data_ptr()) : nullptr;
 }
 
+// an optional flat side tensor of a launch (indices, labels, accumulators): a contiguous GPU tensor
+// of dtype `st` with at least n elements, checked before anything is launched; nullptr when absent
+template <typename T>
+T* opt_vec(const optional<Tensor>& t, at::ScalarType st, int64_t n, const char* op, const char* name) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == st && t->is_contiguous() && t->numel() >= n, op, ": ", name,
+              " must be a contiguous GPU ", st, " tensor of at least ", n, " elements");
+  return static_cast<T*>(t->data_ptr());
+}
+
+// an optional [rows, cols] output of a head next to its input `like`: same dtype, unit inner stride
+void* opt_mat(const optional<Tensor>& t, const Tensor& like, int64_t rows, int64_t cols, const char* op,
+              const char* name) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == like.scalar_type() && t->dim() == 2 && t->stride(1) == 1 &&
+                  t->size(0) >= rows && t->size(1) >= cols,
+              op, ": ", name, " must be a GPU ", like.scalar_type(), " tensor of at least [", rows, ", ", cols,
+              "] with a unit inner stride");
+  return t->data_ptr();
+}
+
 // device epoch counter of graph-replayed steps: one int32 on the GPU
 const int* epoch_counter(const optional<Tensor>& t) {
   if (!t.has_value() || !t->defined()) return nullptr;
@@ -100,12 +121,12 @@ void head_accumulators(Args& a, const optional<Tensor>& loss, const optional<Ten
     if (t->has_value() && (*t)->defined())
       TORCH_CHECK((*t)->scalar_type() == (f64 ? at::kDouble : at::kFloat), what,
                   ": loss / colsum accumulators must be ", f64 ? "fp64 for fp64 data" : "fp32");
-  if (f64) {
-    a.loss64 = ptr_or_null<double>(loss);
-    a.colsum64 = ptr_or_null<double>(colsum);
+  if (f64) {  // loss[slots >= 1], colsum[cols] (a.cols is set)
+    a.loss64 = opt_vec<double>(loss, at::kDouble, 1, what, "loss");
+    a.colsum64 = opt_vec<double>(colsum, at::kDouble, a.cols, what, "colsum");
   } else {
-    a.loss = ptr_or_null<float>(loss);
-    a.colsum = ptr_or_null<float>(colsum);
+    a.loss = opt_vec<float>(loss, at::kFloat, 1, what, "loss");
+    a.colsum = opt_vec<float>(colsum, at::kFloat, a.cols, what, "colsum");
   }
   a.loss_slots = (loss.has_value() && loss->defined()) ? static_cast<int>(loss->numel()) : 1;
 }
@@ -577,6 +598,8 @@ void stage_bwd_op(const Tensor& g, const Tensor& y, const Tensor& dx, at::IntArr
   check_dev(g, "g");
   TORCH_CHECK(g.is_contiguous() && y.is_contiguous() && dx.is_contiguous(), "pz::stage_bwd: contiguous tensors");
   TORCH_CHECK(g.scalar_type() == y.scalar_type() && g.scalar_type() == dx.scalar_type(), "pz::stage_bwd: dtypes");
+  TORCH_CHECK(y.is_cuda() && dx.is_cuda() && y.numel() == g.numel() && dx.numel() == g.numel(),
+              "pz::stage_bwd: g, y and dx must be GPU tensors of one size");
   PZ_HIP_CHECK(pz::stage_bwd(g.data_ptr(), y.data_ptr(), dx.data_ptr(), dt_of(g), g.numel(), make_epi(ei, ef),
                              cur_stream(g)));
 }
@@ -595,6 +618,9 @@ void xent_head_op(const Tensor& logits, const Tensor& labels, int64_t rows_valid
   a.ld = logits.stride(0);
   a.labels = labels.data_ptr<int64_t>();
   a.rows = static_cast<int>(logits.size(0));
+  TORCH_CHECK(rows_valid >= 0 && rows_valid <= logits.size(0), "pz::xent_head: rows_valid ", rows_valid,
+              " is outside [0, ", logits.size(0), "]");
+  TORCH_CHECK(labels.is_cuda() && labels.numel() >= rows_valid, "pz::xent_head: labels must hold rows_valid entries");
   a.rows_valid = static_cast<int>(rows_valid);
   a.cols = static_cast<int>(logits.size(1));
   a.dtype = dt_of(logits);
@@ -608,14 +634,12 @@ void xent_head_op(const Tensor& logits, const Tensor& labels, int64_t rows_valid
   }
   a.loss_scale = loss_scale;
   if (dh.has_value() && dh->defined()) {
-    TORCH_CHECK(dh->scalar_type() == logits.scalar_type() && dh->stride(1) == 1, "pz::xent_head: dh");
-    a.dh = dh->data_ptr();
+    a.dh = opt_mat(dh, logits, a.rows, a.cols, "pz::xent_head", "dh");
     a.ld_dh = dh->stride(0);
   }
   a.grad_scale = grad_scale;
   if (probs.has_value() && probs->defined()) {
-    TORCH_CHECK(probs->scalar_type() == logits.scalar_type() && probs->stride(1) == 1, "pz::xent_head: probs");
-    a.probs = probs->data_ptr();
+    a.probs = opt_mat(probs, logits, a.rows, a.cols, "pz::xent_head", "probs");
     a.ld_probs = probs->stride(0);
   }
   a.epi = make_epi(ei, ef);
@@ -628,10 +652,7 @@ void xent_head_op(const Tensor& logits, const Tensor& labels, int64_t rows_valid
     a.ld_out8 = out8->stride(0);
     a.out8_qscale = f32_scalar_ptr(out8_qscale, "out8_qscale");
     TORCH_CHECK(a.out8_qscale != nullptr, "pz::xent_head: out8 needs out8_qscale");
-    if (amax.has_value() && amax->defined()) {
-      TORCH_CHECK(amax->scalar_type() == at::kFloat, "pz::xent_head: amax must be fp32");
-      a.amax = amax->data_ptr<float>();
-    }
+    a.amax = opt_vec<float>(amax, at::kFloat, 1, "pz::xent_head", "amax");
   }
   a.skip_dh = store_dh ? 0 : 1;
   a.su = scale_upd(su_amax, su_qs, su_headroom, su_maxval);
@@ -652,6 +673,10 @@ void mse_head_op(const Tensor& y, const Tensor& target, int64_t rows_valid, cons
   check_dev(y, "y");
   TORCH_CHECK(y.dim() == 2 && target.dim() == 2 && y.stride(1) == 1 && target.stride(1) == 1, "pz::mse_head: 2-D");
   TORCH_CHECK(y.scalar_type() == target.scalar_type(), "pz::mse_head: dtype mismatch");
+  TORCH_CHECK(rows_valid >= 0 && rows_valid <= y.size(0), "pz::mse_head: rows_valid ", rows_valid, " is outside [0, ",
+              y.size(0), "]");
+  TORCH_CHECK(target.is_cuda() && target.size(0) >= rows_valid && target.size(1) >= y.size(1),
+              "pz::mse_head: target must hold [rows_valid, cols]");
   pz::MseArgs a{};
   a.y = y.data_ptr();
   a.ld_y = y.stride(0);
@@ -664,7 +689,7 @@ void mse_head_op(const Tensor& y, const Tensor& target, int64_t rows_valid, cons
   head_accumulators(a, loss, colsum, a.dtype == pz::DT_F64, "pz::mse_head");
   a.loss_scale = loss_scale;
   if (dh.has_value() && dh->defined()) {
-    a.dh = dh->data_ptr();
+    a.dh = opt_mat(dh, y, a.rows, a.cols, "pz::mse_head", "dh");
     a.ld_dh = dh->stride(0);
   }
   a.grad_scale = grad_scale;
@@ -676,6 +701,7 @@ void mse_head_op(const Tensor& y, const Tensor& target, int64_t rows_valid, cons
 void softmax_rows_op(const Tensor& x, const Tensor& y) {
   check_dev(x, "x");
   TORCH_CHECK(x.is_contiguous() && y.is_contiguous() && x.scalar_type() == y.scalar_type(), "pz::softmax_rows");
+  TORCH_CHECK(y.is_cuda() && y.numel() == x.numel(), "pz::softmax_rows: x and y must be GPU tensors of one size");
   const int cols = static_cast<int>(x.size(-1));
   const int rows = static_cast<int>(x.numel() / std::max<int64_t>(cols, 1));
   PZ_HIP_CHECK(pz::softmax_rows(x.data_ptr(), y.data_ptr(), dt_of(x), rows, cols, cur_stream(x)));
@@ -718,6 +744,9 @@ void sample_rows_op(const Tensor& logits, const Tensor& seq, const Tensor& done,
 void softmax_bwd_op(const Tensor& g, const Tensor& y, const Tensor& dx) {
   check_dev(g, "g");
   TORCH_CHECK(g.is_contiguous() && y.is_contiguous() && dx.is_contiguous(), "pz::softmax_bwd");
+  TORCH_CHECK(y.is_cuda() && dx.is_cuda() && g.scalar_type() == y.scalar_type() && dx.scalar_type() == y.scalar_type() &&
+                  g.numel() == y.numel() && dx.numel() == y.numel(),
+              "pz::softmax_bwd: g, y and dx must be GPU tensors of one dtype and size");
   const int cols = static_cast<int>(y.size(-1));
   const int rows = static_cast<int>(y.numel() / std::max<int64_t>(cols, 1));
   PZ_HIP_CHECK(pz::softmax_bwd(g.data_ptr(), y.data_ptr(), dx.data_ptr(), dt_of(y), rows, cols, cur_stream(g)));
@@ -744,13 +773,16 @@ void gather_rows_op(const Tensor& data, const optional<Tensor>& indices, int64_t
                     double su_maxval) {
   check_dev(data, "data");
   TORCH_CHECK(data.dim() == 2 && out.dim() == 2 && data.stride(1) == 1 && out.stride(1) == 1, "pz::gather_rows: 2-D");
-  TORCH_CHECK(out.size(1) == data.size(1), "pz::gather_rows: width mismatch");
+  TORCH_CHECK(out.is_cuda() && out.size(1) == data.size(1), "pz::gather_rows: width mismatch");
+  TORCH_CHECK(rows_valid >= 0 && rows_valid <= out.size(0), "pz::gather_rows: rows_valid ", rows_valid,
+              " is outside [0, ", out.size(0), "]");
+  constexpr const char* kOp = "pz::gather_rows";
   pz::GatherArgs a{};
   a.data = data.data_ptr();
   a.ld_data = data.stride(0);
   a.data_dtype = dt_of(data);
   a.n_data = data.size(0);
-  a.indices = ptr_or_null<const int64_t>(indices);
+  a.indices = opt_vec<const int64_t>(indices, at::kLong, rows_valid, kOp, "indices");
   a.seed_lo = static_cast<uint32_t>(seed_lo);
   a.seed_hi = static_cast<uint32_t>(seed_hi);
   a.out = out.data_ptr();
@@ -759,16 +791,17 @@ void gather_rows_op(const Tensor& data, const optional<Tensor>& indices, int64_t
   a.rows = static_cast<int>(out.size(0));
   a.rows_valid = static_cast<int>(rows_valid);
   a.cols = static_cast<int>(out.size(1));
-  a.labels_in = ptr_or_null<const int64_t>(labels_in);
-  a.labels_out = ptr_or_null<int64_t>(labels_out);
-  a.picked = ptr_or_null<int64_t>(picked);
+  a.labels_in = opt_vec<const int64_t>(labels_in, at::kLong, a.n_data, kOp, "labels_in");
+  a.labels_out = opt_vec<int64_t>(labels_out, at::kLong, a.rows, kOp, "labels_out");
+  TORCH_CHECK(a.labels_out == nullptr || a.labels_in != nullptr, "pz::gather_rows: labels_out needs labels_in");
+  a.picked = opt_vec<int64_t>(picked, at::kLong, rows_valid, kOp, "picked");
   a.epoch_ptr = epoch_counter(epoch);
   if (out8.has_value() && out8->defined()) {
     TORCH_CHECK(data8.has_value() && data8->defined(), "pz::gather_rows: out8 needs data8");
     const Tensor& d8 = *data8;
     const Tensor& o8 = *out8;
-    TORCH_CHECK(d8.element_size() == 1 && o8.element_size() == 1 && d8.dim() == 2 && o8.dim() == 2 &&
-                    d8.stride(1) == 1 && o8.stride(1) == 1 && d8.size(0) == data.size(0) &&
+    TORCH_CHECK(d8.is_cuda() && o8.is_cuda() && d8.element_size() == 1 && o8.element_size() == 1 &&
+                    d8.dim() == 2 && o8.dim() == 2 && d8.stride(1) == 1 && o8.stride(1) == 1 && d8.size(0) == data.size(0) &&
                     d8.size(1) == data.size(1) && o8.size(0) == out.size(0) && o8.size(1) == out.size(1),
                 "pz::gather_rows: data8 [n_data, cols] / out8 [rows, cols] 1-byte tables");
     a.data8 = static_cast<const uint8_t*>(d8.data_ptr());

@@ -412,19 +412,19 @@ __global__ void __launch_bounds__(256) softmax_bwd_kernel(const T* __restrict__ 
   }
 }
 
-// column sums of a [rows][cols] matrix into fp32 (fp64 for fp64 data). ws == nullptr: atomic per
-// 64-column strip per block; otherwise each block stores its partial row ws[blockIdx.y][c] and
+// column sums of a [rows][cols] matrix of row stride ld into fp32 (fp64 for fp64 data). ws == nullptr:
+// atomic per 64-column strip per block; otherwise each block stores its partial row ws[blockIdx.y][c] and
 // colsum_fold_kernel adds the rows to out in block order — the sum order never depends on which
 // block finished first (deterministic training, PZ_DETERMINISTIC)
 template <typename T, typename A>
 __global__ void __launch_bounds__(256) colsum_kernel(const T* __restrict__ x, A* __restrict__ out, int rows,
-                                                     int cols, int rows_per_block, A* __restrict__ ws) {
+                                                     int cols, int64_t ld, int rows_per_block, A* __restrict__ ws) {
   const int c = blockIdx.x * 64 + (threadIdx.x & 63);
   const int r0 = blockIdx.y * rows_per_block;
   const int r1 = min(rows, r0 + rows_per_block);
   A s = A(0);
   if (c < cols)
-    for (int r = r0 + (threadIdx.x >> 6); r < r1; r += 4) s += static_cast<A>(ldd<T>(x, static_cast<int64_t>(r) * cols + c));
+    for (int r = r0 + (threadIdx.x >> 6); r < r1; r += 4) s += static_cast<A>(ldd<T>(x, static_cast<int64_t>(r) * ld + c));
   __shared__ A part[4][64];
   part[threadIdx.x >> 6][threadIdx.x & 63] = s;
   __syncthreads();
@@ -474,10 +474,11 @@ __global__ void __launch_bounds__(WAVES * 64) xent_head_lean_kernel(XentArgs a) 
   for (int rr = 0; rr < RPW; ++rr) {
     const int row = row0 + rr;
     labels[rr] = row < a.rows_valid ? static_cast<int>(a.labels[row]) : -1;
+    // padding rows are not read: zero logits give se = cols, inv = 0 and so exact zeros
 #pragma unroll
     for (int j = 0; j < NCH; ++j)
-      raw[rr][j] = row < a.rows ? *reinterpret_cast<const uint4*>(logits + static_cast<int64_t>(row) * a.ld + (lane + 64 * j) * 8)
-                                : make_uint4(0, 0, 0, 0);
+      raw[rr][j] = row < a.rows_valid ? *reinterpret_cast<const uint4*>(logits + static_cast<int64_t>(row) * a.ld + (lane + 64 * j) * 8)
+                                      : make_uint4(0, 0, 0, 0);
   }
   const float gs = static_cast<float>(a.grad_scale);
   const float qs8 = OUT8 ? *a.out8_qscale : 1.f;
@@ -801,7 +802,7 @@ hipError_t xent_head(const XentArgs& in, hipStream_t s) {
   if (colsum_direct != nullptr && a.dh != nullptr) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return colsum(a.dh, a.dtype, colsum_direct, acc64 ? DT_F64 : DT_F32, a.rows, a.cols, s);  // ld_dh == cols
+    return colsum(a.dh, a.dtype, colsum_direct, acc64 ? DT_F64 : DT_F32, a.rows, a.cols, s, nullptr, a.ld_dh);
   }
   return hipGetLastError();
 }
@@ -824,7 +825,7 @@ hipError_t mse_head(const MseArgs& in, hipStream_t s) {
   if (colsum_direct != nullptr && a.dh != nullptr) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return colsum(a.dh, a.dtype, colsum_direct, acc64 ? DT_F64 : DT_F32, a.rows, a.cols, s);
+    return colsum(a.dh, a.dtype, colsum_direct, acc64 ? DT_F64 : DT_F32, a.rows, a.cols, s, nullptr, a.ld_dh);
   }
   return hipGetLastError();
 }
@@ -851,21 +852,23 @@ hipError_t softmax_bwd(const void* g, const void* y, void* dx, int dtype, int ro
 
 int colsum_parts(int rows) { return (rows + kColsumRows - 1) / kColsumRows; }
 
-hipError_t colsum(const void* x, int dtype, void* out, int out_dtype, int rows, int cols, hipStream_t s, void* ws) {
+hipError_t colsum(const void* x, int dtype, void* out, int out_dtype, int rows, int cols, hipStream_t s, void* ws,
+                  int64_t ld) {
   if (rows <= 0 || cols <= 0) return hipSuccess;
+  if (ld <= 0) ld = cols;
   const int rpb = kColsumRows;
   const int parts = colsum_parts(rows);
   dim3 grid((cols + 63) / 64, parts);
   PZ_DISPATCH_FLOAT(dtype, T, {
     if (out_dtype == DT_F64) {
       hipLaunchKernelGGL((colsum_kernel<T, double>), grid, dim3(256), 0, s, static_cast<const T*>(x),
-                         static_cast<double*>(out), rows, cols, rpb, static_cast<double*>(ws));
+                         static_cast<double*>(out), rows, cols, ld, rpb, static_cast<double*>(ws));
       if (ws != nullptr)
         hipLaunchKernelGGL(colsum_fold_kernel<double>, dim3((cols + 255) / 256), dim3(256), 0, s,
                            static_cast<const double*>(ws), static_cast<double*>(out), parts, cols);
     } else {
       hipLaunchKernelGGL((colsum_kernel<T, float>), grid, dim3(256), 0, s, static_cast<const T*>(x),
-                         static_cast<float*>(out), rows, cols, rpb, static_cast<float*>(ws));
+                         static_cast<float*>(out), rows, cols, ld, rpb, static_cast<float*>(ws));
       if (ws != nullptr)
         hipLaunchKernelGGL(colsum_fold_kernel<float>, dim3((cols + 255) / 256), dim3(256), 0, s,
                            static_cast<const float*>(ws), static_cast<float*>(out), parts, cols);

@@ -88,7 +88,7 @@ struct GatherArgs {
   int rows, rows_valid, cols;
   const int64_t* labels_in;  // optional [n_data]
   int64_t* labels_out;       // optional [rows]
-  int64_t* picked;           // optional [rows]: chosen data index per row
+  int64_t* picked;           // optional [rows_valid]: chosen data index per row
   const int* epoch_ptr;      // graph-replayed steps: seeds += epoch (gather_seed), read on device
   // optional second table gathered with the same picks: the dataset pre-quantised to e4m3 once
   // (fp8 policy, static scale) -> the first GEMM's fp8 operand, no per-step quantisation pass
@@ -122,11 +122,11 @@ struct SampleArgs {
 };
 hipError_t sample_rows(const SampleArgs& a, hipStream_t s);
 // column sums, out[c] += sum_r x[r][c]; ws (colsum_parts(rows) x cols accumulators of out's dtype):
-// deterministic ordered fold instead of float atomics
+// deterministic ordered fold instead of float atomics; ld: row stride of x in elements (0: cols)
 constexpr int kColsumRows = 256;
 int colsum_parts(int rows);
 hipError_t colsum(const void* x, int dtype, void* out, int out_dtype, int rows, int cols, hipStream_t s,
-                  void* ws = nullptr);
+                  void* ws = nullptr, int64_t ld = 0);
 hipError_t gather_rows(const GatherArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------ optimizer (N6)

@@ -56,3 +56,72 @@ def opt_update_reference(p0, graw, m0, v0, weight, dtype, *, adam, lr, b1, b2, e
     v = v0 * s(b2) + (s(1.0) - s(b2)) * g * g
     denom = v.sqrt() / s(bc2s) + s(eps)
     return p0 - (s(lr) / s(bc1)) * (m / denom), m, v
+
+
+def gather_seed(seed_lo: int, seed_hi: int, epoch: int | None) -> tuple[int, int]:
+    """Minibatch sampler seeds of an epoch (the kernels' ``gather_seed``)."""
+    lo, hi = seed_lo & 0xFFFFFFFF, seed_hi & 0xFFFFFFFF
+    if epoch is not None:
+        lo = (lo + epoch * 0x632BE5AB) & 0xFFFFFFFF
+        hi = (hi ^ epoch) & 0xFFFFFFFF
+    return lo, hi
+
+
+def gather_picks(rows_valid: int, n_data: int, seed_lo: int, seed_hi: int, epoch: int | None = None) -> np.ndarray:
+    """Data rows that ``gather_rows`` samples for output rows 0..rows_valid-1 (int64)."""
+    lo, hi = gather_seed(seed_lo, seed_hi, epoch)
+    row = np.arange(rows_valid, dtype=np.uint64)
+    h = _mix32(_mix32(row ^ np.uint64(lo)) ^ np.uint64(hi))
+    return ((h * np.uint64(n_data)) >> np.uint64(32)).astype(np.int64)
+
+
+def keep2d(rows: int, cols: int, idx_ld: int, seed: tuple[int, int], lid: int, p: float,
+           epoch: int | None = None) -> torch.Tensor:
+    """Bool keep-mask of a [rows, cols] tensor whose element (r, c) has the logical index r * idx_ld + c."""
+    ld = idx_ld if idx_ld > 0 else cols
+    m = keep_mask(rows * ld, seed[0], seed[1], lid, p, epoch).reshape(rows, ld)[:, :cols]
+    return torch.from_numpy(m.copy())
+
+
+# fp64 activations by code (ops.functional ACT_*): forward, and the derivative from the OUTPUT a
+ACT_FWD = {0: lambda z: z, 1: lambda z: torch.where(z > 0, z, torch.zeros_like(z)), 2: torch.sigmoid, 3: torch.tanh}
+ACT_DOUT = {0: torch.ones_like, 1: lambda a: (a > 0).to(a.dtype), 2: lambda a: a * (1 - a), 3: lambda a: 1 - a * a}
+
+
+def stage_fwd_reference(x: torch.Tensor, act: int, keep_pre, keep_post, scale) -> torch.Tensor:
+    """``drop_post(act(drop_pre(x)))`` in x's dtype, one multiply per dropout (``scale`` a tensor of
+    that dtype; a mask of None = no dropout). Dropped elements are +0."""
+    zero = torch.zeros_like(x)
+    v = x if keep_pre is None else torch.where(keep_pre, x * scale, zero)
+    v = ACT_FWD[act](v)
+    return v if keep_post is None else torch.where(keep_post, v * scale, zero)
+
+
+def stage_bwd_reference(g: torch.Tensor, y: torch.Tensor, act: int, keep_pre, keep_post, scale: float) -> torch.Tensor:
+    """fp64 ``g * scale_post keep_post * act'(y / scale_post) * scale_pre keep_pre`` from the stored output y."""
+    g, a = g.double(), y.double()
+    if keep_post is not None:
+        g = g * keep_post.double() * scale
+        a = a / scale if scale != 0.0 else a
+    g = g * ACT_DOUT[act](a)
+    if keep_pre is not None:
+        g = g * keep_pre.double() * scale
+    return g
+
+
+def xent_reference(logits: torch.Tensor, labels: torch.Tensor, rows_valid: int, loss_scale: float, grad_scale: float,
+                   keep=None, scale: float = 1.0) -> dict:
+    """fp64 cross-entropy head over rows [0, rows_valid): ``probs``, ``dh`` = (p - onehot) * grad_scale
+    through the logits' dropout (zero rows past rows_valid), ``loss`` and ``colsum`` with the sums of
+    the absolute values of their terms (``loss_abs``, ``colsum_abs``)."""
+    x = logits.double()
+    rows, cols = x.shape
+    probs = torch.softmax(x, 1)
+    lab = labels[:rows_valid].long()
+    terms = (torch.logsumexp(x[:rows_valid], 1) - x[:rows_valid].gather(1, lab[:, None])[:, 0]) * loss_scale
+    dh = torch.zeros_like(x)
+    dh[:rows_valid] = (probs[:rows_valid] - torch.nn.functional.one_hot(lab, cols)) * grad_scale
+    if keep is not None:
+        dh = dh * keep.double() * scale
+    return {"probs": probs, "dh": dh, "loss": terms.sum().item(), "loss_abs": terms.abs().sum().item(),
+            "colsum": dh.sum(0), "colsum_abs": dh.abs().sum(0)}
