@@ -1158,6 +1158,13 @@ std::string format_json_array_op(const Tensor& t, int64_t level) {
 
 std::string repr_double_op(double x) { return pz::repr_double(x); }
 
+// "family/varV/BMxBN/ekE/splitS" of the GEMM kernel the calling thread launched last (pz_launch.h)
+std::string gemm_last_kernel_op() {
+  const pz::GemmLaunch& g = pz::gemm_last;
+  return std::string(g.family) + "/var" + std::to_string(g.var) + "/" + std::to_string(g.bm) + "x" +
+         std::to_string(g.bn) + "/ek" + std::to_string(g.ek) + "/split" + std::to_string(g.split);
+}
+
 // checkpoint reader (N9): -> (skeleton JSON text, float64 values, int64 [ndim, dims...] records)
 std::tuple<std::string, Tensor, Tensor> scan_json_arrays_op(const std::string& path, const std::string& key) {
   std::string text;
@@ -1286,6 +1293,7 @@ TORCH_LIBRARY(pz, m) {
   m.def("quantize_cols(Tensor w, Tensor(a!) out, Tensor(b!) scale, Tensor(c!) amax) -> ()");
   m.def("format_json_array(Tensor t, int level) -> str");
   m.def("repr_double(float x) -> str");
+  m.def("gemm_last_kernel() -> str");
   m.def("scan_json_arrays(str path, str key) -> (str, Tensor, Tensor)");
   m.def("json_skip_keys(str path, str[] keys) -> str");
 }
@@ -1333,6 +1341,7 @@ TORCH_LIBRARY_IMPL(pz, CPU, m) {
 TORCH_LIBRARY_IMPL(pz, CompositeExplicitAutograd, m) {
   m.impl("pack_segments", TORCH_FN(pack_segments_op));
   m.impl("repr_double", TORCH_FN(repr_double_op));
+  m.impl("gemm_last_kernel", TORCH_FN(gemm_last_kernel_op));
   m.impl("scan_json_arrays", TORCH_FN(scan_json_arrays_op));
   m.impl("json_skip_keys", TORCH_FN(json_skip_keys_op));
 }

@@ -111,6 +111,7 @@ hipError_t launch_generic_out(const GemmArgs& p, hipStream_t s) {
     hipLaunchKernelGGL((gemm_generic_kernel<T, Acc, OutT, float>), grid, dim3(256), 0, s, p);
   else
     hipLaunchKernelGGL((gemm_generic_kernel<T, Acc, OutT, uint16_t>), grid, dim3(256), 0, s, p);
+  gemm_last = {"generic", 0, GT, GT, 0, 1};
   return hipGetLastError();
 }
 

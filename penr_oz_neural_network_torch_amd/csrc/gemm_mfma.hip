@@ -690,7 +690,7 @@ gemm_mfma_kernel(const GemmArgs p) {
   gemm_body<BM, BN, WM, WN, A_KC, B_KC, OutT, AuxT, VAR, EK>(p, xcd_remap(blockIdx.x, gridDim.x));
 }
 
-#include "gemm_w4.h"  // VAR 40: the dX layout on 4-wave workgroups (hipBLASLt's schedule)
+#include "gemm_w4.h"  // VAR 40 / 43: the 4-wave LDS-DMA schedule (hipBLASLt's dX kernel)
 
 // Two independent GEMMs of one layout / epilogue kind in ONE launch (gemm_pair): the first nwg0
 // remapped workgroup ids run GEMM 0, the rest GEMM 1 — e.g. the two skinny weight-gradient GEMMs
@@ -723,6 +723,7 @@ hipError_t launch_cfg(const GemmArgs& p, hipStream_t s) {
   }
   const int nwg = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * (p.split_k > 1 ? p.split_k : 1);
   hipLaunchKernelGGL(kern, dim3(nwg), dim3(C::NT), C::LDS_BYTES, s, p);
+  gemm_last = {"mfma", VAR, BM, BN, EK, p.split_k > 1 ? p.split_k : 1};
   return hipGetLastError();
 }
 
@@ -757,8 +758,8 @@ bool use_bk64(const GemmArgs& p, bool buf) {
   return buf && full && p.K % 64 == 0 && (p.K / 64) % split == 0;
 }
 
-// VAR 40 / 42 for the bf16 / fp8 dX layout (gemm_w4.h); PZ_GEMM_W4=0 keeps those GEMMs on VAR 30 /
-// VAR 9, 17 (A/B)
+// VAR 40 for the bf16 dX layout and VAR 43 for the long-K plain fp8 forward (gemm_w4.h);
+// PZ_GEMM_W4=0 keeps those GEMMs on VAR 30 / VAR 15, 16 (A/B)
 bool w4_default() {
   static const bool on = [] {
     const char* e = getenv("PZ_GEMM_W4");
@@ -786,6 +787,21 @@ int epi_kind(const GemmArgs& p) {
   return EK_ANY;
 }
 
+// forward layout (A K-contiguous, B N-contiguous): a tile config's instantiation for epilogue kind ek
+// — the fixed stages, the ReLU stage where the config has one (RELU), else the generic epilogue
+template <int BM, int BN, int WM, int WN, typename OutT, typename AuxT, int VAR, bool RELU = true>
+hipError_t launch_fwd_kind(int ek, const GemmArgs& p, hipStream_t s) {
+  switch (ek) {
+    case EK_F_RELU_POST: return launch_cfg<BM, BN, WM, WN, true, false, OutT, AuxT, VAR, EK_F_RELU_POST>(p, s);
+    case EK_F_RELU_PREPOST: return launch_cfg<BM, BN, WM, WN, true, false, OutT, AuxT, VAR, EK_F_RELU_PREPOST>(p, s);
+    case EK_F_PRE: return launch_cfg<BM, BN, WM, WN, true, false, OutT, AuxT, VAR, EK_F_PRE>(p, s);
+    case EK_RELU:
+      if constexpr (RELU) return launch_cfg<BM, BN, WM, WN, true, false, OutT, AuxT, VAR, EK_RELU>(p, s);
+      [[fallthrough]];
+    default: return launch_cfg<BM, BN, WM, WN, true, false, OutT, AuxT, VAR>(p, s);
+  }
+}
+
 // the MLP's three GEMM layouts on the 64-deep ring, each with its stage's specialised epilogue:
 // forward X·W (K-contiguous x N-contiguous), dX = dZ·Wᵀ (both K-contiguous), dW = Xᵀ·dZ (both
 // M/N-contiguous); anything else takes the generic epilogue
@@ -793,13 +809,7 @@ template <typename OutT, typename AuxT, int VAR>
 hipError_t launch_bk64_256(const GemmArgs& p, hipStream_t s) {
   if constexpr (std::is_same<OutT, uint16_t>::value) {
     const int ek = epi_kind(p);
-    if (p.a_kc && !p.b_kc) {
-      if (ek == EK_RELU) return launch_cfg<256, 256, 2, 4, true, false, OutT, AuxT, VAR, EK_RELU>(p, s);
-      if (ek == EK_F_RELU_POST) return launch_cfg<256, 256, 2, 4, true, false, OutT, AuxT, VAR, EK_F_RELU_POST>(p, s);
-      if (ek == EK_F_RELU_PREPOST)
-        return launch_cfg<256, 256, 2, 4, true, false, OutT, AuxT, VAR, EK_F_RELU_PREPOST>(p, s);
-      if (ek == EK_F_PRE) return launch_cfg<256, 256, 2, 4, true, false, OutT, AuxT, VAR, EK_F_PRE>(p, s);
-    }
+    if (p.a_kc && !p.b_kc) return launch_fwd_kind<256, 256, 2, 4, OutT, AuxT, VAR>(ek, p, s);
     if (p.a_kc && p.b_kc && ek == EK_BWD_MASK)
       return launch_cfg<256, 256, 2, 4, true, true, OutT, AuxT, VAR, EK_BWD_MASK>(p, s);
     if (!p.a_kc && !p.b_kc && ek == EK_STORE) return launch_cfg<256, 256, 2, 4, false, false, OutT, AuxT, VAR, EK_STORE>(p, s);
@@ -833,7 +843,7 @@ hipError_t launch_tiles(const GemmArgs& p, hipStream_t s) {
   if constexpr (std::is_same<OutT, uint16_t>::value) {
     const int ek = epi_kind(p);
     if (w4_default() && w4_eligible(p, ek))
-      return ek == EK_BWD_MASK ? launch_w4<EK_BWD_MASK>(p, s) : launch_w4<EK_STORE>(p, s);
+      return ek == EK_BWD_MASK ? launch_w4<W4Bf16, EK_BWD_MASK>(p, s) : launch_w4<W4Bf16, EK_STORE>(p, s);
   }
   // buffer-addressed LDS-DMA (VAR 6; +2..12% on the step's shapes, tools/gemm_lab)
   if (tiles(256, 256) >= kFill) {
@@ -842,12 +852,8 @@ hipError_t launch_tiles(const GemmArgs& p, hipStream_t s) {
   }
   if (tiles(256, 128) >= kFill) {
     if constexpr (std::is_same<OutT, uint16_t>::value) {
-      if (bk64 && w128_fixed(p)) {
-        const int ek = epi_kind(p);
-        if (ek == EK_F_RELU_POST) return launch_cfg<256, 128, 4, 2, true, false, OutT, AuxT, 30, EK_F_RELU_POST>(p, s);
-        if (ek == EK_F_RELU_PREPOST) return launch_cfg<256, 128, 4, 2, true, false, OutT, AuxT, 30, EK_F_RELU_PREPOST>(p, s);
-        if (ek == EK_F_PRE) return launch_cfg<256, 128, 4, 2, true, false, OutT, AuxT, 30, EK_F_PRE>(p, s);
-      }
+      // (no ReLU-stage form of this config: w128_fixed takes the fixed kinds only)
+      if (bk64 && w128_fixed(p)) return launch_fwd_kind<256, 128, 4, 2, OutT, AuxT, 30, false>(epi_kind(p), p, s);
     }
     if (bk64) return launch_layout<256, 128, 4, 2, OutT, AuxT, 30>(p, s);
     return buf ? launch_layout<256, 128, 4, 2, OutT, AuxT, 6>(p, s) : launch_layout<256, 128, 4, 2, OutT, AuxT>(p, s);
@@ -871,33 +877,19 @@ hipError_t launch_fp8(const GemmArgs& p, hipStream_t s) {
   // VAR 43: the fp8 forward on the 4-wave LDS-DMA schedule, plain stores at K >= 2048 (at K = 1,024 it
   // ties VAR 16). With the fused stage epilogues the 32x32 accumulator layout's 128-column wave rows
   // (16 four-column groups per lane: values, column sums, bias) spill 66-213 VGPRs — the fused fp8 dX
-  // (VAR 42, tools/gemm_w4f8_lab.hip) ran 144 vs 106 us in the mlp8192 step (profiles/r6_gemm_w4.txt) —
+  // (VAR 42, tools/gemm_w4_lab_ops.h) ran 144 vs 106 us in the mlp8192 step (profiles/r6_gemm_w4.txt) —
   // so the trainer's fused fp8 GEMMs stay on VAR 9 / 15-17
-  if (w4_default() && ek == EK_STORE && p.K >= 2048 && w4f8_fwd_eligible(p, ek)) return launch_w4f8<EK_STORE, false>(p, s);
+  if (w4_default() && ek == EK_STORE && p.K >= 2048 && w4f8_fwd_eligible(p, ek)) return launch_w4<W4F8Fwd, EK_STORE>(p, s);
   if (f8_two_wg(p)) {
-    if (p.a_kc && !p.b_kc) {
-      if (ek == EK_RELU) return launch_cfg<256, 128, 2, 2, true, false, uint16_t, uint16_t, 16, EK_RELU>(p, s);
-      if (ek == EK_F_RELU_POST) return launch_cfg<256, 128, 2, 2, true, false, uint16_t, uint16_t, 16, EK_F_RELU_POST>(p, s);
-      if (ek == EK_F_RELU_PREPOST)
-        return launch_cfg<256, 128, 2, 2, true, false, uint16_t, uint16_t, 16, EK_F_RELU_PREPOST>(p, s);
-      if (ek == EK_F_PRE) return launch_cfg<256, 128, 2, 2, true, false, uint16_t, uint16_t, 16, EK_F_PRE>(p, s);
-      return launch_cfg<256, 128, 2, 2, true, false, uint16_t, uint16_t, 16>(p, s);
-    }
+    if (p.a_kc && !p.b_kc) return launch_fwd_kind<256, 128, 2, 2, uint16_t, uint16_t, 16>(ek, p, s);
     if (p.a_kc && p.b_kc && p.a_fmt == 1) {
       if (ek == EK_BWD_MASK) return launch_cfg<256, 128, 2, 2, true, true, uint16_t, uint16_t, 17, EK_BWD_MASK>(p, s);
       return launch_cfg<256, 128, 2, 2, true, true, uint16_t, uint16_t, 17>(p, s);
     }
   }
-  if (p.a_kc && !p.b_kc) {  // e4m3 X x e4m3 W[in, out] (fp8_eligible: N % 256 — B's transposed image
-                           // rows are whole 256-B tiles, swz_mn8 — buffer-addressable B; split-K
-                           // when the tiles do not fill the CUs, gemm_split)
-    if (ek == EK_RELU) return launch_cfg<256, 256, 2, 4, true, false, uint16_t, uint16_t, 15, EK_RELU>(p, s);
-    if (ek == EK_F_RELU_POST) return launch_cfg<256, 256, 2, 4, true, false, uint16_t, uint16_t, 15, EK_F_RELU_POST>(p, s);
-    if (ek == EK_F_RELU_PREPOST)
-      return launch_cfg<256, 256, 2, 4, true, false, uint16_t, uint16_t, 15, EK_F_RELU_PREPOST>(p, s);
-    if (ek == EK_F_PRE) return launch_cfg<256, 256, 2, 4, true, false, uint16_t, uint16_t, 15, EK_F_PRE>(p, s);
-    return launch_cfg<256, 256, 2, 4, true, false, uint16_t, uint16_t, 15>(p, s);
-  }
+  // e4m3 X x e4m3 W[in, out] (fp8_eligible: N % 256 — B's transposed image rows are whole 256-B
+  // tiles, swz_mn8 — buffer-addressable B; split-K when the tiles do not fill the CUs, gemm_split)
+  if (p.a_kc && !p.b_kc) return launch_fwd_kind<256, 256, 2, 4, uint16_t, uint16_t, 15>(ek, p, s);
   // (measured, not kept: buffer-addressed staging, VAR 10 / 11; the 64-deep ring, VAR 12 / 13,
   // within noise of the 32-deep one, profiles/r2_ab_fp8_bk64.txt)
   if (ek_fixed(ek)) ek = EK_RELU;  // (VAR 8 forms: the generic ReLU-stage kind)
@@ -928,6 +920,7 @@ hipError_t launch_pair_cfg(const GemmPairArgs& g, int nwg, hipStream_t s) {
     attr_set = true;
   }
   hipLaunchKernelGGL(kern, dim3(nwg), dim3(C::NT), C::LDS_BYTES, s, g);
+  gemm_last = {"pair", VAR, 256, 256, EK, g.p[0].split_k > 1 ? g.p[0].split_k : 1};
   return hipGetLastError();
 }
 

@@ -492,6 +492,7 @@ hipError_t sk_launch(const SkArgs& a, hipStream_t st) {
     attr_set = true;
   }
   hipLaunchKernelGGL(kern, dim3(a.s.grid), dim3(SkGeo<W>::NT), kSkLds, st, a);
+  gemm_last = {"sk", 0, kSkB, kSkB, EK, 1};
   return hipGetLastError();
 }
 

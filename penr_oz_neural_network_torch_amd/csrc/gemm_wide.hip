@@ -222,6 +222,7 @@ hipError_t launch_wide_k(const GemmArgs& p, hipStream_t s) {
   }
   const int nwg = ((p.M + WT - 1) / WT) * ((p.N + WT - 1) / WT);
   hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, s, p);
+  gemm_last = {"wide", 0, WT, WT, 0, 1};
   return hipGetLastError();
 }
 

@@ -143,6 +143,17 @@ hipError_t gemm_pair(const GemmArgs& a, const GemmArgs& b, hipStream_t stream);
 // exposed for tests / benchmarks: which path gemm() would take
 int gemm_path(const GemmArgs& args);  // 0 = generic VALU, 1 = MFMA bf16 / fp8, 2 = MFMA fp32 / fp64
 
+// The GEMM kernel this thread launched last. Every launcher writes it next to its launch, so it
+// cannot disagree with what ran (gemm_path only predicts the path): family "generic", "wide",
+// "mfma" (the tiled kernels), "w4" (gemm_w4.h), "sk" (stream-K) or "pair"; the kernel's VAR number
+// (0 where the family has none), output tile, epilogue kind (gemm_epilogue.h EK_*; 0 = EK_ANY where
+// the family has none) and split-K factor
+struct GemmLaunch {
+  const char* family;
+  int var, bm, bn, ek, split;
+};
+inline thread_local GemmLaunch gemm_last = {"none", 0, 0, 0, 0, 1};
+
 // Skinny-batch forward GEMM of the inference path (gemm_skinny.hip): out[M][N] = act(x[M][K] ·
 // W[K][N] + bias), 1 <= M <= 16, W N-contiguous, x of W's type (bf16 / fp32), fp32 accumulation.
 // A separate op: gemm() never selects it.

@@ -183,6 +183,18 @@ def gemm_path(a: Tensor, a_kc: bool, b: Tensor, b_kc: bool, out: Tensor) -> str:
     return {1: "mfma", 2: "mfma_wide"}.get(path, "generic")  # mfma_wide: fp32 / fp64 matrix cores
 
 
+def gemm_last_kernel() -> str:
+    """The GEMM kernel the calling thread launched last, recorded by the launcher itself (unlike
+    :func:`gemm_path`, which predicts): ``"family/varV/BMxBN/ekE/splitS"``, e.g.
+    ``"w4/var40/256x256/ek3/split1"``. ``family`` is ``generic`` (VALU tile), ``wide`` (fp32 / fp64
+    matrix cores), ``mfma`` (the tiled bf16 / fp8 kernels), ``w4`` (the 4-wave LDS-DMA schedule),
+    ``sk`` (stream-K) or ``pair`` (``gemm_pair``), ``none`` before the first launch; ``V`` the kernel
+    variant (0 where the family has none); ``BMxBN`` the output tile; ``E`` the epilogue kind (0 any,
+    1 plain store, 2 ReLU stage, 3 ReLU-bitmask backward, 4-6 the fixed dropout stages; always 0 for
+    ``generic`` / ``wide``); ``S`` the split-K factor (1 = none)."""
+    return _ops().gemm_last_kernel()
+
+
 SKINNY_MAX_ROWS = 16
 
 
@@ -667,7 +679,7 @@ def tensor_summary(t: Tensor, algo: str | None, bins: int) -> dict:
     return out
 
 
-__all__ = ["gemm", "gemm_path", "gemm_skinny", "gemm_skinny_eligible", "gemm_skinny_w8", "gemm_skinny_w8_eligible",
+__all__ = ["gemm", "gemm_path", "gemm_last_kernel", "gemm_skinny", "gemm_skinny_eligible", "gemm_skinny_w8", "gemm_skinny_w8_eligible",
            "quantize_cols", "quantize_cols_reference", "dequantize_cols", "linear", "activation", "dropout", "softmax", "cross_entropy", "mse_loss",
            "batchnorm", "embedding", "tensor_summary", "epi_spec", "new_seed", "sample_rows", "sample_rows_reference",
            "sample_uniform"]

@@ -126,7 +126,9 @@ def test_sk_matches_tiled_engine_bitwise_on_whole_tiles(native_lib):
     o1 = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
     o2 = torch.empty_like(o1)
     PF.gemm(a, True, b, False, o1, engine=1)
+    assert PF.gemm_last_kernel() == "mfma/var30/256x256/ek0/split1"
     PF.gemm(a, True, b, False, o2, engine=2, cus=256)
+    assert PF.gemm_last_kernel() == "sk/var0/256x256/ek1/split1"
     assert torch.equal(o1, o2)
 
 

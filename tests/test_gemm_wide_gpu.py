@@ -45,6 +45,7 @@ def test_gemm_fp32_matrix_cores(native_lib, a_kc, b_kc):
     out = torch.empty(M, N, device=DEV, dtype=torch.float32)
     assert PF.gemm_path(a, a_kc, b, b_kc, out) == "mfma_wide"
     PF.gemm(a, a_kc, b, b_kc, out)
+    assert PF.gemm_last_kernel() == "wide/var0/128x128/ek0/split1"
     ref, scale = _ref(a, a_kc, b, b_kc)
     rel = ((out.double().cpu() - ref).abs() / scale).max().item()
     assert rel < 2e-6, rel

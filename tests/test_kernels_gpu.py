@@ -58,6 +58,7 @@ def test_gemm_generic_small(native_lib, dtype):
     out = torch.empty(M, N, device=DEV, dtype=dtype)
     assert PF.gemm_path(a, True, b, False, out) == "generic"
     PF.gemm(a, True, b, False, out, bias=bias)
+    assert PF.gemm_last_kernel() == "generic/var0/64x64/ek0/split1"
     ref = a.double() @ b.double() + bias.double()
     tol = {torch.float64: 1e-12, torch.float32: 1e-4, torch.bfloat16: 0.15}[dtype]
     assert (out.double() - ref).abs().max().item() < tol
@@ -174,11 +175,9 @@ def test_gemm_relu_bitmask_forward_and_backward(native_lib, M, N, K):
     assert (out_bit.double() - ref).abs().max().item() < 0.02 * ref.abs().max().item()
 
 
-@pytest.mark.parametrize("M,N,K", [(4096, 4096, 128), (4096, 4096, 320), (8192, 4096, 1024)])
-def test_gemm_w4_dx_engine(native_lib, M, N, K):
-    """VAR 40 (csrc/gemm_w4.h: 4-wave LDS-DMA kernel for the dX layout, whole 256-tiles that fill
-    the CUs): plain store and the ReLU-bitmask backward epilogue with column sums == fp64 torch, at
-    the minimum two K steps, an odd step count and the mlp4 dX_L3 shape."""
+def _dx_plain_and_bitmask_backward(M, N, K, kernel_plain, kernel_bwd):
+    """A dX-layout bf16 GEMM with a plain store, then with the ReLU-bitmask backward epilogue and
+    column sums == fp64 torch, each launched as the named kernel (PF.gemm_last_kernel)."""
     p, seed = 0.2, (7, 9)
     g = torch.Generator(device="cpu").manual_seed(M + K)
     gz = torch.randn(M, K, generator=g).to(DEV, torch.bfloat16)
@@ -186,15 +185,34 @@ def test_gemm_w4_dx_engine(native_lib, M, N, K):
     ref = gz.double() @ wt.double().t()
     out = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
     PF.gemm(gz, True, wt, True, out)
+    assert PF.gemm_last_kernel() == kernel_plain
     assert (out.double() - ref).abs().max().item() < 1e-3 * math.sqrt(K) + 0.01 * ref.abs().max().item()
     yb = torch.randn(M, N, generator=g).to(DEV) > 0
     mask = PF.relu_mask_pack(yb)
     epi = PF.epi_spec(act=PF.ACT_RELU, drop_pre=1, drop_post=2, p=p, seed=seed)
     cs = torch.zeros(N, device=DEV)
     PF.gemm(gz, True, wt, True, out, colsum=cs, mode=PF.EPI_BWD, epi=epi, mask=mask)
+    assert PF.gemm_last_kernel() == kernel_bwd
     refb = ref * yb.double() / (1 - p) ** 2
     assert (out.double() - refb).abs().max().item() < 0.01 * refb.abs().max().item()
     assert (cs.double() - out.double().sum(0)).abs().max().item() < 2e-3 * out.double().abs().sum(0).max().item()
+
+
+@pytest.mark.parametrize("M,N,K", [(4096, 4096, 128), (4096, 4096, 320), (8192, 4096, 1024)])
+def test_gemm_w4_dx_engine(native_lib, M, N, K):
+    """VAR 40 (csrc/gemm_w4.h: 4-wave LDS-DMA kernel for the dX layout, whole 256-tiles that fill
+    the CUs): plain store and the ReLU-bitmask backward epilogue with column sums == fp64 torch, at
+    the minimum two K steps, an odd step count and the mlp4 dX_L3 shape."""
+    _dx_plain_and_bitmask_backward(M, N, K, "w4/var40/256x256/ek1/split1", "w4/var40/256x256/ek3/split1")
+
+
+@pytest.mark.parametrize("M,N,K,plain,bwd", [
+    (3584, 4096, 128, "mfma/var30/256x128/ek0/split1", "mfma/var30/256x128/ek0/split1"),
+    (4096, 4096, 64, "mfma/var30/256x256/ek0/split1", "mfma/var30/256x256/ek3/split1")])
+def test_gemm_w4_dx_fallbacks(native_lib, M, N, K, plain, bwd):
+    """Just outside VAR 40's conditions the dX GEMMs stay on the 8-wave 64-deep ring (VAR 30): 224
+    tiles do not fill the CUs (256x128 tiles, generic epilogue), K = 64 is a single K step."""
+    _dx_plain_and_bitmask_backward(M, N, K, plain, bwd)
 
 
 @pytest.mark.parametrize("M,N,K", [(512, 256, 128), (8192, 8192, 1024), (300, 264, 192)])
@@ -227,6 +245,8 @@ def test_gemm_fp8_e5m2_backward(native_lib, M, N, K):
                 scale_b=sb)
     else:
         PF.gemm(g8, True, w8, True, out, aux=y, colsum=colsum, mode=PF.EPI_BWD, epi=epi, scale_a=qs[1:2], scale_b=sb)
+    # the fp8 dX stays on VAR 9 / 17: the 4-wave schedule's fp8 dX form (VAR 42) is not dispatched
+    assert PF.gemm_last_kernel().startswith("mfma/"), PF.gemm_last_kernel()
     h = (g8.double() @ w8.double().t()) * (qs[1].double() / 16)
     scale = 1.0 / (1 - p) ** 2  # relu' x both dropout scales (y > 0 implies kept by both)
     ref = h * (y.double() > 0) * scale
@@ -305,11 +325,13 @@ def test_gemm_fp8_forward(native_lib, M, N, K):
     assert amax_skip.item() == amax.item()
 
 
-@pytest.mark.parametrize("M,N,K", [(512, 256, 128), (4096 + 64, 1024, 512), (8192, 8192, 1024), (8192, 1024, 8192)])
+@pytest.mark.parametrize("M,N,K", [(512, 256, 128), (4096 + 64, 1024, 512), (8192, 8192, 1024), (8192, 1024, 8192),
+                                   (4096, 4096, 2048)])
 def test_gemm_fp8_forward_natural_weights(native_lib, M, N, K):
     """fp8 forward on the [in, out] e4m3 weights (B N-contiguous, transposing 8-bit LDS reads;
     256x256 tiles, ragged M, split-K on the skinny shape) with the fused stage epilogue == the same
-    GEMM on the transposed [out, in] copy."""
+    GEMM on the transposed [out, in] copy. The fused epilogue never runs on the 4-wave schedule
+    (VAR 43 takes plain stores only), not even at the shape where the plain forward does."""
     f8 = torch.float8_e4m3fn
     p, seed = 0.1, (3, 4)
     x8 = (torch.randn(M, K, device=DEV) * 4).to(f8)
@@ -327,6 +349,9 @@ def test_gemm_fp8_forward_natural_weights(native_lib, M, N, K):
         assert PF.gemm_path(x8, True, w, kc, y) == "mfma"
         PF.gemm(x8, True, w, kc, y, bias=bias, mode=PF.EPI_FWD, epi=epi, scale_a=sa, scale_b=sb, out8=y8,
                 out8_qscale=torch.tensor([8.0], device=DEV), amax=amax, mask=mask)
+        assert PF.gemm_last_kernel().startswith("mfma/"), PF.gemm_last_kernel()
+        if (M, N, K) == (4096, 4096, 2048) and not kc:
+            assert PF.gemm_last_kernel() == "mfma/var15/256x256/ek5/split1"
         outs.append((y, y8, mask, amax))
     (y, y8, mask, amax), (yt, y8t, maskt, amaxt) = outs
     h = (x8.double() @ w8n.double()) * (0.125 / 64) + bias.double()
@@ -340,10 +365,11 @@ def test_gemm_fp8_forward_natural_weights(native_lib, M, N, K):
     assert abs(amax.item() - amaxt.item()) <= 2 ** -7 * amaxt.item()
 
 
-@pytest.mark.parametrize("M,N,K", [(4096, 4096, 2048), (8192, 4096, 4096)])
+@pytest.mark.parametrize("M,N,K", [(4096, 4096, 2048), (8192, 4096, 4096), (4096, 4096, 1024)])
 def test_gemm_w4_fp8_forward_plain(native_lib, M, N, K):
     """VAR 43 (csrc/gemm_w4.h, plain stores, K >= 2048): e4m3 activations x the [in, out] e4m3 weights
-    == fp64 torch on the same fp8 values with the per-tensor scales applied."""
+    == fp64 torch on the same fp8 values with the per-tensor scales applied; below K = 2048 the same
+    GEMM stays on VAR 15."""
     g = torch.Generator(device="cpu").manual_seed(K)
     sa, sb = torch.tensor([0.25], device=DEV), torch.tensor([1.0 / 32], device=DEV)
     x4 = (torch.randn(M, K, generator=g) * 4).to(DEV).to(torch.float8_e4m3fn)
@@ -351,6 +377,7 @@ def test_gemm_w4_fp8_forward_plain(native_lib, M, N, K):
     out = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
     assert PF.gemm_path(x4, True, w4n, False, out) == "mfma"
     PF.gemm(x4, True, w4n, False, out, scale_a=sa, scale_b=sb)
+    assert PF.gemm_last_kernel() == ("w4/var43/256x256/ek1/split1" if K >= 2048 else "mfma/var15/256x256/ek0/split1")
     ref = (x4.double() @ w4n.double()) * (0.25 / 32)
     assert (out.double() - ref).abs().max().item() < 0.01 * ref.abs().max().item()
 

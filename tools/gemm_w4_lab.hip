@@ -7,6 +7,7 @@
 //         tools/gemm_w4_lab.hip -o tools/gemm_w4_lab && tools/gemm_w4_lab
 #define PZ_GEMM_LAB 1
 #include "../penr_oz_neural_network_torch_amd/csrc/gemm_mfma.hip"
+#include "gemm_w4_lab_ops.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -780,10 +781,10 @@ int main(int argc, char** argv) {
   // dX_*: B [N][K] (K-contiguous); fwd_*: B [K][N] (N-contiguous, the forward's weights). Earlier
   // variants (w4::launch_dma<D4>, launch_dmap<D4, MODE> diagnostics) stay instantiable here.
   const std::vector<V> dx = {{"lib_var30", launch_cfg<256, 256, 2, 4, true, true, uint16_t, uint16_t, 30>},
-                             {"var40", launch_w4<EK_STORE, true>}, {"dmap4_full", w4::launch_dmap<4, 3>},
+                             {"var40", launch_w4<W4Bf16, EK_STORE>}, {"dmap4_full", w4::launch_dmap<4, 3>},
                              {"dmap8_nodma", w4::launch_dmap<8, 2>}};
   const std::vector<V> fw = {{"lib_var30", launch_cfg<256, 256, 2, 4, true, false, uint16_t, uint16_t, 30>},
-                             {"var41", launch_w4<EK_STORE, false>}};
+                             {"var41", launch_w4<W4Bf16Fwd, EK_STORE>}};
   std::vector<Case> cases = {{"dX_L2", 8192, 4096, 4096, true, dx}, {"dX_L3", 8192, 4096, 1024, true, dx},
                              {"fwd_L2", 8192, 4096, 4096, false, fw}, {"fwd_L1", 8192, 4096, 1024, false, fw}};
   hipStream_t st;

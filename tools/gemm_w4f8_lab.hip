@@ -1,4 +1,4 @@
-// Lab: VAR 42 / 43 (csrc/gemm_w4.h: the 4-wave LDS-DMA schedule on the fp8 scale MFMA) against the
+// Lab: VAR 42 / 43 (csrc/gemm_w4.h, tools/gemm_w4_lab_ops.h: the 4-wave LDS-DMA schedule on the fp8 scale MFMA) against the
 // library's fp8 kernels on the fp8 policy's shapes, bf16 out, plain store: dX = e5m2 dZ [M][K] x e4m3
 // W [N][K] (both K-contiguous) vs VAR 17; forward = e4m3 X [M][K] x e4m3 W [K][N] vs VAR 15 / 16.
 //
@@ -6,6 +6,7 @@
 //         tools/gemm_w4f8_lab.hip -o tools/gemm_w4f8_lab && tools/gemm_w4f8_lab
 #define PZ_GEMM_LAB 1
 #include "../penr_oz_neural_network_torch_amd/csrc/gemm_mfma.hip"
+#include "gemm_w4_lab_ops.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -62,10 +63,10 @@ int main() {
   struct Case { const char* name; int M, N, K; bool fwd; std::vector<V> vs; };
   // dX: e5m2 dZ [M][K] x e4m3 W [N][K]; fwd: e4m3 X [M][K] x e4m3 W [K][N] (the natural [in, out] copy)
   const std::vector<V> dx = {{"var17", launch_cfg<256, 128, 2, 2, true, true, uint16_t, uint16_t, 17>},
-                             {"var42", launch_w4f8<EK_STORE, true>}};
+                             {"var42", launch_w4<W4F8Dx, EK_STORE>}};
   const std::vector<V> fw = {{"var16", launch_cfg<256, 128, 2, 2, true, false, uint16_t, uint16_t, 16>},
                              {"var15", launch_cfg<256, 256, 2, 4, true, false, uint16_t, uint16_t, 15>},
-                             {"var43", launch_w4f8<EK_STORE, false>}};
+                             {"var43", launch_w4<W4F8Fwd, EK_STORE>}};
   std::vector<Case> cases = {{"f8_dX_8k", 8192, 8192, 1024, false, dx}, {"f8_dX_L2", 8192, 4096, 4096, false, dx},
                              {"f8_fwd_8k", 8192, 8192, 1024, true, fw}, {"f8_fwd_L2", 8192, 4096, 4096, true, fw}};
   hipStream_t st;
