@@ -14,8 +14,10 @@
 
 #include <torch/library.h>
 
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <tuple>
 #include <vector>
 
@@ -216,8 +218,21 @@ int* split_counters(int tiles, const c10::Device& dev) {
 
 const float* f32_scalar_ptr(const optional<Tensor>& t, const char* what) {
   if (!t.has_value() || !t->defined()) return nullptr;
-  TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() >= 1, "pz::gemm: ", what, " must be an fp32 device scalar");
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->numel() >= 1, "pz: ", what,
+              " must be an fp32 device scalar");
   return t->data_ptr<float>();
+}
+
+// a flat fp32 side array a kernel reads or writes (scale records, amax accumulators): on the GPU,
+// contiguous, at least n elements, checked before anything is launched
+float* f32_dev_vec(const Tensor& t, int64_t n, const char* op, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() >= n, op, ": ", name,
+              " must be a contiguous GPU fp32 tensor of at least ", n, " elements");
+  return t.data_ptr<float>();
+}
+float* f32_dev_vec(const optional<Tensor>& t, int64_t n, const char* op, const char* name) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  return f32_dev_vec(*t, n, op, name);
 }
 
 // a folded fp8 scale update (pz_kernels.h ScaleUpd) riding on another launch
@@ -929,16 +944,24 @@ void segment_stats_op(const Tensor& params, const Tensor& segments, const Tensor
 // ----------------------------------------------------------------------------------- stats
 void tensor_moments_op(const Tensor& x, int64_t row_len, int64_t rule, double thr, const Tensor& out) {
   check_dev(x, "x");
-  TORCH_CHECK(x.is_contiguous() && out.scalar_type() == at::kDouble && out.numel() >= 8, "pz::tensor_moments");
+  TORCH_CHECK(x.is_contiguous() && out.is_cuda() && out.scalar_type() == at::kDouble && out.is_contiguous() &&
+                  out.numel() >= 8,
+              "pz::tensor_moments: contiguous x, out must be a contiguous GPU fp64 tensor of >= 8 elements");
+  TORCH_CHECK(rule >= 0 && rule <= pz::SAT_ROW_MAX_GT, "pz::tensor_moments: unknown saturation rule ", rule);
+  TORCH_CHECK(row_len >= 0, "pz::tensor_moments: negative row_len");
   PZ_HIP_CHECK(pz::tensor_moments(x.data_ptr(), dt_of(x), x.numel(), row_len, static_cast<int>(rule),
                                   static_cast<float>(thr), out.data_ptr<double>(), cur_stream(x)));
 }
 
 void histogram_op(const Tensor& x, const Tensor& range, int64_t bins, const Tensor& counts) {
   check_dev(x, "x");
-  TORCH_CHECK(x.is_contiguous() && range.scalar_type() == at::kDouble && counts.scalar_type() == at::kLong &&
-                  counts.is_contiguous() && counts.numel() >= bins,
-              "pz::histogram: counts must be a contiguous int64 tensor of >= bins elements");
+  // one u32 LDS counter per bin: 8192 bins are 32 KB of the block's LDS
+  TORCH_CHECK(bins >= 1 && bins <= 8192, "pz::histogram: bins must be in [1, 8192], got ", bins);
+  TORCH_CHECK(x.is_contiguous() && counts.is_cuda() && counts.scalar_type() == at::kLong && counts.is_contiguous() &&
+                  counts.numel() >= bins,
+              "pz::histogram: counts must be a contiguous GPU int64 tensor of >= bins elements");
+  TORCH_CHECK(range.is_cuda() && range.scalar_type() == at::kDouble && range.is_contiguous() && range.numel() >= 2,
+              "pz::histogram: range must be a contiguous GPU fp64 tensor {lo, hi}");
   PZ_HIP_CHECK(pz::histogram(x.data_ptr(), dt_of(x), x.numel(), range.data_ptr<double>(), static_cast<int>(bins),
                              counts.data_ptr<int64_t>(), cur_stream(x)));
 }
@@ -1039,15 +1062,17 @@ void embedding_bwd_op(const Tensor& dout, const Tensor& idx, const Tensor& dtabl
 // ------------------------------------------------------------------------------------ fp8
 void amax_abs_op(const Tensor& x, const Tensor& amax) {
   check_dev(x, "x");
-  TORCH_CHECK(x.is_contiguous() && amax.scalar_type() == at::kFloat, "pz::amax_abs: contiguous x, fp32 amax");
-  PZ_HIP_CHECK(pz::amax_abs(x.data_ptr(), dt_of(x), x.numel(), amax.data_ptr<float>(), cur_stream(x)));
+  TORCH_CHECK(x.is_contiguous(), "pz::amax_abs: contiguous x");
+  PZ_HIP_CHECK(pz::amax_abs(x.data_ptr(), dt_of(x), x.numel(), f32_dev_vec(amax, 1, "pz::amax_abs", "amax"),
+                            cur_stream(x)));
 }
 
 void scale_update_op(const Tensor& amax, const Tensor& qs, double headroom, bool reset, double maxval) {
   check_dev(amax, "amax");
-  TORCH_CHECK(amax.scalar_type() == at::kFloat && qs.scalar_type() == at::kFloat && qs.numel() >= 2 * amax.numel(),
-              "pz::scale_update: fp32 amax[n], qs[2n]");
-  PZ_HIP_CHECK(pz::scale_update(amax.data_ptr<float>(), qs.data_ptr<float>(), static_cast<int>(amax.numel()),
+  TORCH_CHECK(amax.numel() <= std::numeric_limits<int>::max() / 2, "pz::scale_update: too many scales");
+  float* amax_p = f32_dev_vec(amax, 0, "pz::scale_update", "amax");
+  float* qs_p = f32_dev_vec(qs, 2 * amax.numel(), "pz::scale_update", "qs");
+  PZ_HIP_CHECK(pz::scale_update(amax_p, qs_p, static_cast<int>(amax.numel()),
                                 static_cast<float>(headroom), reset, cur_stream(amax), static_cast<float>(maxval)));
 }
 
@@ -1055,18 +1080,21 @@ void quant_transpose_op(const Tensor& w, const Tensor& out, const Tensor& qs, co
                         const optional<Tensor>& amax_clear) {
   check_dev(w, "w");
   TORCH_CHECK(w.scalar_type() == at::kFloat && w.dim() == 2 && w.stride(1) == 1, "pz::quant_transpose: fp32 [K,N] w");
-  TORCH_CHECK(out.scalar_type() == at::kFloat8_e4m3fn && out.dim() == 2 && out.stride(1) == 1 &&
-                  out.size(0) == w.size(1) && out.size(1) == w.size(0) && out.stride(0) % 4 == 0,
-              "pz::quant_transpose: out must be e4m3 [N,K]");
-  TORCH_CHECK(qs.scalar_type() == at::kFloat && qs.numel() >= 2, "pz::quant_transpose: fp32 qs[2]");
+  // the kernels store packed 4-byte words at out + n * ldo + 4 j: the base and the row stride are 4-byte aligned
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat8_e4m3fn && out.dim() == 2 && out.stride(1) == 1 &&
+                  out.size(0) == w.size(1) && out.size(1) == w.size(0) && out.stride(0) % 4 == 0 &&
+                  (reinterpret_cast<uintptr_t>(out.data_ptr()) & 3) == 0,
+              "pz::quant_transpose: out must be a GPU e4m3 [N,K] with a 4-byte aligned base and row stride");
+  TORCH_CHECK(out.size(0) <= 1 || out.stride(0) >= out.size(1), "pz::quant_transpose: out rows overlap");
   const bool fused = amax.has_value() && amax->defined();
-  TORCH_CHECK(!fused || (amax_clear.has_value() && amax_clear->defined() && amax->scalar_type() == at::kFloat &&
-                         amax_clear->scalar_type() == at::kFloat && amax->numel() >= 1 && amax_clear->numel() >= 1),
+  TORCH_CHECK(!fused || (amax_clear.has_value() && amax_clear->defined()),
               "pz::quant_transpose: fp32 amax and amax_clear go together");
+  float* qs_p = f32_dev_vec(qs, 2, "pz::quant_transpose", "qs");
+  float* amax_p = f32_dev_vec(amax, 1, "pz::quant_transpose", "amax");
+  float* clear_p = fused ? f32_dev_vec(amax_clear, 1, "pz::quant_transpose", "amax_clear") : nullptr;
   PZ_HIP_CHECK(pz::quant_transpose(w.data_ptr<float>(), w.stride(0), static_cast<int>(w.size(0)),
                                    static_cast<int>(w.size(1)), static_cast<uint8_t*>(out.data_ptr()), out.stride(0),
-                                   qs.data_ptr<float>(), fused ? amax->data_ptr<float>() : nullptr,
-                                   fused ? amax_clear->data_ptr<float>() : nullptr, cur_stream(w)));
+                                   qs_p, amax_p, clear_p, cur_stream(w)));
 }
 
 void quantize_rows_op(const Tensor& x, const Tensor& out, const Tensor& qs, const optional<Tensor>& amax,
@@ -1077,11 +1105,20 @@ void quantize_rows_op(const Tensor& x, const Tensor& out, const Tensor& qs, cons
                   (out.scalar_type() == at::kFloat8_e4m3fn || e5m2) && out.size(0) >= x.size(0) &&
                   out.size(1) >= x.size(1) && out.stride(0) % 4 == 0 && x.size(1) % 4 == 0,
               "pz::quantize_rows: x [rows, cols % 4 == 0], out e4m3 / e5m2 [rows, cols]");
+  // both kernels store packed words of 4 codes at out + r * ldo + 4 j (the 8-wide one, chosen by the
+  // launcher only for an 8-byte aligned base, two of them at once)
+  TORCH_CHECK(out.is_cuda() && (reinterpret_cast<uintptr_t>(out.data_ptr()) & 3) == 0,
+              "pz::quantize_rows: out must be a GPU tensor with a 4-byte aligned base");
+  TORCH_CHECK(x.size(0) <= 1 || out.stride(0) >= x.size(1), "pz::quantize_rows: out rows overlap");
+  const bool derived = amax_in.has_value() && amax_in->defined();
+  // the derived scale publishes {q, 1/q}; a given scale is only read (qs[0])
+  float* qs_p = f32_dev_vec(qs, derived ? 2 : 1, "pz::quantize_rows", "qs");
+  float* amax_p = f32_dev_vec(amax, 1, "pz::quantize_rows", "amax");
+  float* clear_p = f32_dev_vec(amax_clear, 1, "pz::quantize_rows", "amax_clear");
   PZ_HIP_CHECK(pz::quantize_rows(x.data_ptr(), dt_of(x), x.stride(0), static_cast<int>(x.size(0)),
                                  static_cast<int>(x.size(1)), static_cast<uint8_t*>(out.data_ptr()), out.stride(0),
-                                 qs.data_ptr<float>(), amax.has_value() ? amax->data_ptr<float>() : nullptr,
-                                 cur_stream(x), e5m2 ? 1 : 0, f32_scalar_ptr(amax_in, "amax_in"),
-                                 amax_clear.has_value() ? amax_clear->data_ptr<float>() : nullptr));
+                                 qs_p, amax_p, cur_stream(x), e5m2 ? 1 : 0, f32_scalar_ptr(amax_in, "amax_in"),
+                                 clear_p));
 }
 
 // w [K,N] fp32 -> out [K,N] e4m3 (same layout) + one power-of-two scale per column; amax is the

@@ -9,6 +9,13 @@
 // is quantised once, quantize_rows, and the minibatch gather copies its e4m3 rows).
 //
 // Scale records are fp32 device arrays {q, s} so no host sync is ever needed.
+//
+// Rounding: finite values go to the nearest code, ties to the even code, the sign of zero is kept,
+// and anything past the largest finite value (+-448 e4m3, +-57344 e5m2; +-inf included) saturates
+// there: byte for byte torch's CPU cast of the clamped value. NaN inputs are NOT propagated:
+// fmaxf / fminf drop a NaN operand, so a NaN quantises to the most negative code (-448 / -57344) and
+// the amax reductions ignore it. The fused e4m3 / e5m2 copies of the GEMM and head epilogues share
+// this rule.
 #include <cstdlib>
 
 #include "pz_common.h"

@@ -5,6 +5,11 @@
 // Here one moments pass (min/max/sum/sum^2/saturation count, exact orderable-key atomics for
 // min/max) and one 100-bin LDS histogram pass run on the device; only ~1 KB per tensor crosses
 // to the host.
+//
+// Bins: a value v in [lo, hi] goes to bin int((v - lo) * (bins / (hi - lo))), hi itself to the last
+// bin, values outside the range and NaN to none. torch.histogram instead compares v with bin edges
+// it builds by linspace, so a value within rounding of an edge of a non-dyadic range can land one bin
+// away from torch's; where every edge is exactly representable (dyadic ranges) the two agree.
 #include "pz_common.h"
 #include "pz_kernels.h"
 
@@ -150,6 +155,7 @@ hipError_t tensor_moments(const void* x, int dtype, int64_t n, int64_t row_len, 
 }
 
 hipError_t histogram(const void* x, int dtype, int64_t n, const double* range, int bins, int64_t* counts, hipStream_t s) {
+  if (bins <= 0) return hipErrorInvalidValue;  // (the clamp to bins - 1 would index LDS at -1)
   if (n <= 0) return hipSuccess;
   PZ_STATS_DISPATCH(dtype, T, {
     hipLaunchKernelGGL((histogram_kernel<T>), dim3(grid_stride_blocks(n)), dim3(256), bins * sizeof(unsigned int), s,

@@ -12,7 +12,10 @@ Histograms follow ``torch.histogram(t, density=True)`` semantics: 100 bins over
 
 CPU tensors use ATen (identical to the reference). GPU tensors use the fused ``pz`` stats
 kernels (one pass for min/max/sum/sum²/saturation + one histogram pass; ``torch.histogram`` has
-no GPU kernel) and a single device→host copy per tensor.
+no GPU kernel) and a single device→host copy per tensor. The GPU histogram bins a value by
+``int((v - lo) * (bins / (hi - lo)))`` where ``torch.histogram`` compares it with ``linspace`` edges:
+a value within rounding of a bin edge can be counted one bin away from torch's (never lost), and
+only ranges whose edges are exactly representable agree count for count.
 """
 from __future__ import annotations
 

@@ -125,3 +125,65 @@ def xent_reference(logits: torch.Tensor, labels: torch.Tensor, rows_valid: int, 
         dh = dh * keep.double() * scale
     return {"probs": probs, "dh": dh, "loss": terms.sum().item(), "loss_abs": terms.abs().sum().item(),
             "colsum": dh.sum(0), "colsum_abs": dh.abs().sum(0)}
+
+
+# ------------------------------------------------------------------------------------------- fp8
+# (exponent bits, mantissa bits, bias, largest finite code) of the two OCP 8-bit formats
+_FP8 = {torch.float8_e4m3fn: (4, 3, 7, 0x7E), torch.float8_e5m2: (5, 2, 15, 0x7B)}
+
+
+def fp8_code_values(fmt) -> np.ndarray:
+    """The finite non-negative values of ``fmt`` by code (fp64, ascending: index == code), from the
+    format's definition: 2^(1 - bias) * m / 2^mbits for exponent field 0, 2^(e - bias) * (1 + m / 2^mbits)
+    otherwise. e4m3fn: 0 .. 0x7E (448; 0x7F is NaN), e5m2: 0 .. 0x7B (57344; 0x7C is inf)."""
+    _, mbits, bias, last = _FP8[fmt]
+    code = np.arange(last + 1)
+    e, m = code >> mbits, (code & ((1 << mbits) - 1)).astype(np.float64)
+    return np.where(e == 0, np.ldexp(m, 1 - bias - mbits), np.ldexp(1.0 + np.ldexp(m, -mbits), e - bias))
+
+
+def fp8_encode_reference(values_fp64, fmt) -> torch.Tensor:
+    """uint8 codes of the nearest finite ``fmt`` value of each fp64 input: ties go to the even code,
+    the sign bit is the input's (zero included), |v| past the largest finite value (inf included)
+    saturates there. Built from the code table alone: the two neighbouring codes and their midpoint
+    (a sum of two neighbours halves exactly in fp64), no float8 cast of the input. NaN is not handled."""
+    v = np.asarray(torch.as_tensor(values_fp64, dtype=torch.float64).numpy())
+    assert not np.isnan(v).any()
+    table = fp8_code_values(fmt)
+    last = len(table) - 1
+    a = np.minimum(np.abs(v), table[last])
+    lo = np.searchsorted(table, a, side="right") - 1   # table[lo] <= a
+    hi = np.minimum(lo + 1, last)
+    mid = (table[lo] + table[hi]) / 2
+    code = np.where(a > mid, hi, np.where(a < mid, lo, np.where(lo % 2 == 0, lo, hi)))
+    code = np.where(lo == hi, lo, code)
+    return torch.from_numpy((code | np.where(np.signbit(v), 0x80, 0)).astype(np.uint8))
+
+
+def fp8_tie_points(fmt) -> torch.Tensor:
+    """fp32 points where an fp8 rounding rule can go wrong: every finite non-negative code value,
+    every midpoint of two neighbouring codes, the fp32 neighbour of each midpoint on both sides,
+    2^-149, 2^-126, 1.5 * max, 1e30 and +inf; all of them with both signs (no NaN)."""
+    table = fp8_code_values(fmt)
+    codes = torch.from_numpy(table).float()
+    assert torch.equal(codes.double(), torch.from_numpy(table))
+    mids = (codes[:-1] + codes[1:]) / 2
+    assert torch.equal(mids.double() * 2, torch.from_numpy(table[:-1] + table[1:]))
+    inf = torch.tensor(float("inf"))
+    extra = torch.tensor([2.0 ** -149, 2.0 ** -126, 1.5 * table[-1], 1e30, float("inf")], dtype=torch.float32)
+    pos = torch.cat([codes, mids, torch.nextafter(mids, -inf), torch.nextafter(mids, inf), extra])
+    return torch.cat([pos, -pos])
+
+
+def histogram_reference(values, lo: float, hi: float, bins: int) -> np.ndarray:
+    """int64 counts of ``bins`` equal bins over [lo, hi] (the last one closed) by integer arithmetic.
+    ``values`` (any float tensor; NaN allowed, never counted), ``lo`` and ``hi`` must be multiples of
+    1/8: the value k/8 then lies in bin floor((k - 8 lo) * bins / (8 hi - 8 lo)), a quotient of
+    integers, and ``hi`` itself in the last bin."""
+    v = torch.as_tensor(values).double().numpy().ravel()
+    v = v[~np.isnan(v)] * 8
+    k, lo8, hi8 = np.rint(v).astype(np.int64), int(round(lo * 8)), int(round(hi * 8))
+    assert np.array_equal(k.astype(np.float64), v) and lo8 == lo * 8 and hi8 == hi * 8 and hi8 > lo8
+    k = k[(k >= lo8) & (k <= hi8)]
+    b = np.minimum(((k - lo8) * bins) // (hi8 - lo8), bins - 1)
+    return np.bincount(b, minlength=bins).astype(np.int64)
