@@ -135,6 +135,10 @@ class GenerateRequest(ModelRequest):
     stop_token: int | None = Field(None, description="A row ends with its first occurrence of this id (inclusive).")
     pad_token: int = Field(0, description="Id that left-pads short context rows.")
     weights: str | None = Field(None, description="'fp8': weight-only e4m3 copies, as on /predict/.")
+    loop: str | None = Field(None, description="'resident': the whole request as one GPU launch with the model held in "
+                                               "on-chip memory (GPU models whose parameters fit in 160 KiB, at most "
+                                               "8192 classes; anything else answers 400 with the reason). Omitted: "
+                                               "one sampling launch per token.")
 
 
 class TrainingRequest(ModelRequest):
@@ -310,9 +314,11 @@ def generate_tokens(body: GenerateRequest = Body(..., openapi_examples=GENERATE_
     model_id = body.model_id
     log.info(f"Requesting generation for model {model_id}")
     model = _cached_model(model_id)
+    extra = {} if body.loop is None else {"loop": body.loop}  # (only when asked for, as weights on /predict/)
     try:
         return model.generate(body.context, body.max_new_tokens, temperature=body.temperature, top_k=body.top_k,
-                              seed=body.seed, stop_token=body.stop_token, pad_token=body.pad_token, weights=body.weights)
+                              seed=body.seed, stop_token=body.stop_token, pad_token=body.pad_token, weights=body.weights,
+                              **extra)
     except IndexError as e:  # a context id outside the vocabulary is a bad request
         raise ValueError(str(e))
 

@@ -9,6 +9,7 @@
 #include <unistd.h>
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
+#include <algorithm>
 #include <map>
 #include <mutex>
 
@@ -756,6 +757,145 @@ void sample_rows_op(const Tensor& logits, const Tensor& seq, const Tensor& done,
   PZ_HIP_CHECK(pz::sample_rows(a, cur_stream(logits)));
 }
 
+// a whole generation request in one launch (csrc/generate_resident.hip). `plan` is the int list of
+// engine/resident.py: resident_plan. Whatever a wrong plan could turn into a stray LDS or global
+// access is refused here: the kernel trusts every number it is handed.
+void generate_resident_op(const Tensor& seq, const Tensor& done, at::TensorList params, at::IntArrayRef plan, int64_t steps,
+                          double temperature, int64_t top_k, int64_t seed_lo, int64_t seed_hi, int64_t stop_token,
+                          int64_t row0, const optional<Tensor>& logits_out) {
+  const char* who = "pz::generate_resident: ";
+  check_dev(seq, "seq");
+  check_dev(done, "done");
+  TORCH_CHECK(steps >= 1 && steps <= pz::kResMaxSteps, who, "steps must be in [1, ", pz::kResMaxSteps, "], got ", steps);
+  TORCH_CHECK(temperature >= 0.0, who, "temperature must be >= 0 and not NaN, got ", temperature);
+  TORCH_CHECK(top_k >= 0, who, "top_k must be >= 0 (0 = off)");
+  TORCH_CHECK(static_cast<int64_t>(plan.size()) >= pz::kResHead && static_cast<int64_t>(plan.size()) <= pz::kResPlanMax,
+              who, "plan of ", plan.size(), " ints");
+  for (const int64_t v : plan)
+    TORCH_CHECK(v >= INT32_MIN && v <= static_cast<int64_t>(UINT32_MAX), who, "plan entry ", v, " is no 32-bit value");
+  auto P = [&](int64_t i) { return static_cast<int>(static_cast<uint32_t>(plan[i])); };
+  TORCH_CHECK(P(pz::RH_MAGIC) == pz::kResMagic, who, "not a resident plan");
+  const int L = P(pz::RH_L), E = P(pz::RH_E), vocab = P(pz::RH_VOCAB), V = P(pz::RH_V);
+  const int ns = P(pz::RH_STAGES), np = P(pz::RH_PARAMS), esize = P(pz::RH_ESIZE), total = P(pz::RH_TOTAL);
+  const int64_t buf_bytes = P(pz::RH_BUF_BYTES);
+  TORCH_CHECK(ns >= 1 && ns <= pz::kResMaxStages && np >= 1 && np <= pz::kResMaxParams, who, "stage / parameter count");
+  TORCH_CHECK(static_cast<int64_t>(plan.size()) == pz::kResHead + np * pz::kResParam + ns * pz::kResStage, who,
+              "plan length does not match its counts");
+  TORCH_CHECK(static_cast<int64_t>(params.size()) == np, who, "plan names ", np, " parameters, got ", params.size());
+  TORCH_CHECK(esize == 2 || esize == 4, who, "compute element size must be 2 or 4");
+  TORCH_CHECK(L >= 1 && L <= 65536 && E >= 1 && E <= 65536, who, "context length / embedding width out of range");
+  TORCH_CHECK(V >= 1 && V <= pz::kSampleNarrowCols, who, "V must be in [1, ", pz::kSampleNarrowCols, "], got ", V);
+  TORCH_CHECK(vocab >= V, who, "the table has ", vocab, " rows but the model predicts ", V, " classes");
+  TORCH_CHECK(static_cast<int64_t>(vocab) * E <= INT32_MAX / 4, who, "embedding table too large");
+
+  int dev_lds = 0;
+  PZ_HIP_CHECK(hipDeviceGetAttribute(&dev_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, seq.device().index()));
+  TORCH_CHECK(total >= 0 && total % 16 == 0 && total + pz::generate_resident_static_lds() <= dev_lds, who, "plan needs ",
+              total, " bytes of LDS, the device gives a workgroup ", dev_lds);
+
+  // every LDS region: 16-byte aligned, inside the total, and apart from the others
+  std::vector<std::pair<int64_t, int64_t>> regions;
+  auto region = [&](int64_t off, int64_t bytes, const char* what) {
+    TORCH_CHECK(off >= 0 && off % 16 == 0 && bytes >= 0 && off + bytes <= total, who, what, " at offset ", off, " (", bytes,
+                " bytes) lies outside the plan's ", total, " bytes or is misaligned");
+    regions.emplace_back(off, off + bytes);
+  };
+  region(P(pz::RH_OFF_WIN), 4 * (static_cast<int64_t>(L) + 1), "window");
+  region(P(pz::RH_OFF_BUF0), buf_bytes, "buffer 0");
+  region(P(pz::RH_OFF_BUF1), buf_bytes, "buffer 1");
+  region(P(pz::RH_OFF_LOGITS), 4 * static_cast<int64_t>(V), "logits");
+  region(P(pz::RH_OFF_SAMPLER), pz::kSampleScratchBytes, "sampler scratch");
+  region(P(pz::RH_OFF_PARTIAL), pz::kResPartialBytes, "partial sums");
+
+  // parameters: tensor against plan
+  const int64_t par0 = pz::kResHead, stg0 = par0 + static_cast<int64_t>(np) * pz::kResParam;
+  for (int p = 0; p < np; ++p) {
+    const Tensor& t = params[p];
+    const int off = P(par0 + p * pz::kResParam + pz::RP_OFF), numel = P(par0 + p * pz::kResParam + pz::RP_NUMEL);
+    const int es = P(par0 + p * pz::kResParam + pz::RP_ESIZE);
+    TORCH_CHECK(t.is_cuda() && t.device() == seq.device() && t.is_contiguous(), who, "parameter ", p,
+                " must be a contiguous tensor on seq's device");
+    TORCH_CHECK((es == 4 && t.scalar_type() == at::kFloat) || (es == 2 && t.scalar_type() == at::kBFloat16), who, "parameter ",
+                p, " has dtype ", t.scalar_type(), ", the plan expects ", es, "-byte elements");
+    TORCH_CHECK(numel >= 1 && t.numel() == numel, who, "parameter ", p, " has ", t.numel(), " elements, the plan expects ", numel);
+    if (p == 0) {
+      TORCH_CHECK(es == 4 && numel == static_cast<int64_t>(vocab) * E, who, "parameter 0 must be the fp32 [", vocab, ", ", E, "] table");
+      TORCH_CHECK((P(pz::RH_TABLE_LDS) != 0) == (off >= 0), who, "table placement flag and offset disagree");
+      if (off < 0) continue;
+    }
+    region(off, static_cast<int64_t>(numel) * es, "parameter");
+  }
+  auto param_is = [&](int idx, int64_t numel, int es, const char* what) {
+    TORCH_CHECK(idx >= 1 && idx < np, who, what, ": parameter index ", idx, " out of range");
+    TORCH_CHECK(P(par0 + idx * pz::kResParam + pz::RP_NUMEL) == numel && P(par0 + idx * pz::kResParam + pz::RP_ESIZE) == es, who,
+                what, ": parameter ", idx, " does not have ", numel, " elements of ", es, " bytes");
+  };
+
+  // stages: shapes chain from [L, E] to [1, V], every output fits its buffer
+  TORCH_CHECK(static_cast<int64_t>(L) * E * esize <= buf_bytes, who, "the embedding output does not fit the buffers");
+  int64_t cur_p = L, cur_w = E;
+  for (int s = 0; s < ns; ++s) {
+    const int64_t b = stg0 + static_cast<int64_t>(s) * pz::kResStage;
+    const int kind = P(b + pz::RS_KIND), sp = P(b + pz::RS_P), sk = P(b + pz::RS_K), sn = P(b + pz::RS_N), act = P(b + pz::RS_ACT);
+    TORCH_CHECK(kind >= 0 && kind <= 2 && sp >= 1 && sk >= 1 && sn >= 1 && act >= 0 && act <= 3, who, "stage ", s, " is malformed");
+    if (kind == 0) {
+      TORCH_CHECK(cur_p % sk == 0 && sp == cur_p / sk && sn == cur_w * sk, who, "flatten stage ", s, " does not follow its input");
+    } else if (kind == 1) {
+      TORCH_CHECK(sp == cur_p && sk == cur_w, who, "linear stage ", s, " does not follow its input");
+      param_is(P(b + pz::RS_PA), static_cast<int64_t>(sk) * sn, esize, "linear weights");
+      if (P(b + pz::RS_PB) != -1) param_is(P(b + pz::RS_PB), sn, 4, "linear bias");
+    } else {
+      TORCH_CHECK(sp == cur_p && sk == cur_w && sn == cur_w, who, "batchnorm stage ", s, " does not follow its input");
+      param_is(P(b + pz::RS_PA), sn, 4, "batchnorm gain");
+      param_is(P(b + pz::RS_PB), sn, 4, "batchnorm bias");
+      param_is(P(b + pz::RS_PM), sn, 4, "batchnorm running mean");
+      param_is(P(b + pz::RS_PV), sn, 4, "batchnorm running variance");
+      region(P(b + pz::RS_OFF_INV), 8 * static_cast<int64_t>(sn), "batchnorm scratch");
+    }
+    cur_p = sp;
+    cur_w = sn;
+    TORCH_CHECK(cur_p * cur_w <= INT32_MAX / 8, who, "stage ", s, " is too large");
+    if (s == ns - 1) {
+      TORCH_CHECK(kind == 1 && cur_p == 1 && cur_w == V, who, "the last stage must be a linear stage giving one row of ", V, " logits");
+    } else {
+      TORCH_CHECK(cur_p * cur_w * esize <= buf_bytes, who, "stage ", s, " does not fit the buffers");
+    }
+  }
+  std::sort(regions.begin(), regions.end());
+  for (size_t i = 1; i < regions.size(); ++i)
+    TORCH_CHECK(regions[i - 1].second <= regions[i].first, who, "LDS regions overlap at offset ", regions[i].first);
+
+  TORCH_CHECK(seq.scalar_type() == at::kLong && seq.dim() == 2 && seq.is_contiguous(), who,
+              "seq must be a contiguous int64 [rows, L + steps] tensor");
+  TORCH_CHECK(seq.size(1) == L + steps, who, "seq has ", seq.size(1), " columns, expected L + steps = ", L + steps);
+  const int64_t rows = seq.size(0);
+  TORCH_CHECK(rows <= INT32_MAX, who, "too many rows");
+  TORCH_CHECK(done.scalar_type() == at::kInt && done.dim() == 1 && done.is_contiguous() && done.size(0) == rows &&
+                  done.device() == seq.device(),
+              who, "done must be a contiguous int32 [rows] tensor on seq's device");
+  pz::ResidentArgs a{};
+  if (logits_out.has_value() && logits_out->defined()) {
+    const Tensor& lo = *logits_out;
+    TORCH_CHECK(lo.is_cuda() && lo.device() == seq.device() && lo.scalar_type() == at::kFloat && lo.is_contiguous() &&
+                    lo.dim() == 3 && lo.size(0) == rows && lo.size(1) == steps && lo.size(2) == V,
+                who, "logits_out must be a contiguous fp32 [rows, steps, V] tensor on seq's device");
+    a.logits_out = lo.data_ptr<float>();
+  }
+  a.seq = seq.data_ptr<int64_t>();
+  a.done = done.data_ptr<int>();
+  for (int p = 0; p < np; ++p) a.params[p] = params[p].data_ptr();
+  for (size_t i = 0; i < plan.size(); ++i) a.plan[i] = P(static_cast<int64_t>(i));
+  a.rows = static_cast<int>(rows);
+  a.steps = static_cast<int>(steps);
+  a.temperature = static_cast<float>(temperature);
+  a.top_k = static_cast<int>(std::min<int64_t>(top_k, V));
+  a.seed_lo = static_cast<uint32_t>(seed_lo);
+  a.seed_hi = static_cast<uint32_t>(seed_hi);
+  a.row0 = static_cast<uint32_t>(row0);
+  a.stop_token = stop_token;
+  PZ_HIP_CHECK(pz::generate_resident(a, cur_stream(seq)));
+}
+
 void softmax_bwd_op(const Tensor& g, const Tensor& y, const Tensor& dx) {
   check_dev(g, "g");
   TORCH_CHECK(g.is_contiguous() && y.is_contiguous() && dx.is_contiguous(), "pz::softmax_bwd");
@@ -1294,6 +1434,8 @@ TORCH_LIBRARY(pz, m) {
   m.def("softmax_rows(Tensor x, Tensor(a!) y) -> ()");
   m.def("sample_rows(Tensor logits, Tensor(a!) seq, Tensor(b!) done, int pos, float temperature, int top_k, int key, "
         "int stop_token=-1, int row0=0) -> ()");
+  m.def("generate_resident(Tensor(a!) seq, Tensor(b!) done, Tensor[] params, int[] plan, int steps, float temperature, "
+        "int top_k, int seed_lo, int seed_hi, int stop_token=-1, int row0=0, Tensor(c!)? logits_out=None) -> ()");
   m.def("softmax_bwd(Tensor g, Tensor y, Tensor(a!) dx) -> ()");
   m.def("colsum(Tensor x, Tensor(a!) out) -> ()");
   m.def("gather_rows(Tensor data, Tensor? indices, int seed_lo, int seed_hi, Tensor(a!) out, int rows_valid, "
@@ -1352,6 +1494,7 @@ TORCH_LIBRARY_IMPL(pz, CUDA, m) {
   m.impl("mse_head", TORCH_FN(mse_head_op));
   m.impl("softmax_rows", TORCH_FN(softmax_rows_op));
   m.impl("sample_rows", TORCH_FN(sample_rows_op));
+  m.impl("generate_resident", TORCH_FN(generate_resident_op));
   m.impl("softmax_bwd", TORCH_FN(softmax_bwd_op));
   m.impl("colsum", TORCH_FN(colsum_op));
   m.impl("gather_rows", TORCH_FN(gather_rows_op));

@@ -121,6 +121,38 @@ struct SampleArgs {
   int64_t stop_token;   // -1 = none
 };
 hipError_t sample_rows(const SampleArgs& a, hipStream_t s);
+constexpr int kSampleNarrowCols = 8192;     // up to here a row is sampled by 256 threads (sample_core.h)
+constexpr int kSampleScratchBytes = 16912;  // sizeof(SampleScratch): the sampler's LDS per workgroup
+
+// one-launch token generation with the whole model in LDS (generate_resident.hip). The plan is
+// engine/resident.py's int list: kResHead header ints, kResParam per parameter, kResStage per stage.
+constexpr int kResMaxStages = 16, kResMaxParams = 64, kResMaxSteps = 4096;
+constexpr int kResHead = 20, kResParam = 3, kResStage = 12;
+constexpr int kResPlanMax = kResHead + kResMaxParams * kResParam + kResMaxStages * kResStage;
+constexpr int kResMagic = 0x5A52;
+constexpr int kResPartialBytes = 1024;      // K-split partial sums: 256 floats
+enum ResHead {  // header slots
+  RH_MAGIC = 0, RH_L, RH_E, RH_VOCAB, RH_V, RH_STAGES, RH_PARAMS, RH_TABLE_LDS, RH_ESIZE, RH_BUF_BYTES,
+  RH_OFF_WIN, RH_OFF_BUF0, RH_OFF_BUF1, RH_OFF_LOGITS, RH_OFF_SAMPLER, RH_OFF_PARTIAL, RH_TOTAL
+};
+enum ResParam { RP_OFF = 0, RP_NUMEL, RP_ESIZE };  // off < 0: the parameter stays in global memory
+enum ResStage {  // kind: 0 flatten (K = ratio), 1 gemm, 2 bn; PA..PV index the parameter list (-1: none)
+  RS_KIND = 0, RS_P, RS_K, RS_N, RS_ACT, RS_PA, RS_PB, RS_PM, RS_PV, RS_OFF_INV, RS_EPS_LO, RS_EPS_HI
+};
+struct ResidentArgs {
+  int64_t* seq;        // [rows][L + steps]: the context, then the tokens
+  int* done;           // [rows]
+  float* logits_out;   // [rows][steps][V] or null
+  const void* params[kResMaxParams];
+  int plan[kResPlanMax];
+  int rows, steps;
+  float temperature;
+  int top_k;
+  uint32_t seed_lo, seed_hi, row0;
+  int64_t stop_token;
+};
+int generate_resident_static_lds();  // LDS the kernel holds outside its dynamic region (0 expected)
+hipError_t generate_resident(const ResidentArgs& a, hipStream_t s);
 // column sums, out[c] += sum_r x[r][c]; ws (colsum_parts(rows) x cols accumulators of out's dtype):
 // deterministic ordered fold instead of float atomics; ld: row stride of x in elements (0: cols)
 constexpr int kColsumRows = 256;

@@ -1,0 +1,232 @@
+// pz::sample_row — steps 1-3c of the sampling rule described in sample.hip (row maximum, exact top-k
+// threshold, segment sums, prefix scan and the walk), as one device function shared by
+// sample_rows_kernel (logits in global memory, one call per launch) and generate_resident_kernel
+// (logits in LDS, one call per token of a loop). One code, one set of instructions: the same logits,
+// scalars and (row, key) give the same token in both.
+//
+// Every thread of the NT-thread workgroup calls it (it holds __syncthreads()); there is no early
+// return, so a loop may call it again. The token comes back in every lane of wave 0 (in every thread
+// when temperature == 0); the other waves' return value is meaningless. A caller that repeats the call
+// puts a barrier between two calls: the greedy path reads best_w after its only barrier, and the next
+// call's first write goes to best_w.
+#pragma once
+
+#include "pz_common.h"
+#include "pz_kernels.h"
+
+namespace pz {
+
+constexpr int kSegments = 64;      // one per lane of the selecting wave
+constexpr int kSampleMaxWaves = 16;
+constexpr int kSampleLoads = 16;   // loads in flight per thread
+constexpr int kDigits = 3;         // key digits from the top: 12, 10 and 10 bits
+constexpr int kMaxBins = 1 << 12;
+constexpr int kBins = 1 << 10;
+
+// the LDS a workgroup needs for one row (16.5 KiB), wherever the kernel keeps it
+struct alignas(16) SampleScratch {
+  unsigned long long best_w[kSampleMaxWaves];
+  int hist[kMaxBins];
+  int wtot[kSampleMaxWaves];
+  int sel[2];
+  int lastk_w[kSampleMaxWaves];
+  float segsum[kSegments];
+};
+static_assert(sizeof(SampleScratch) == kSampleScratchBytes, "pz_kernels.h: kSampleScratchBytes");
+
+// order-preserving image of a float: a > b (as floats, -0 == +0) <=> okey(a) > okey(b)
+PZ_DEV uint32_t okey(float x) {
+  uint32_t u = __float_as_uint(x);
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+PZ_DEV float okey_inv(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+
+template <typename T>
+PZ_DEV T scan_incl(T v, int lane) {
+#pragma unroll
+  for (int d = 1; d < kWave; d <<= 1) {
+    const T t = __shfl_up(v, d, kWave);
+    if (lane >= d) v += t;
+  }
+  return v;
+}
+
+// f(c, x[c]) for c = first, first + stride, ... < n (any order-free fold): kSampleLoads loads, then their uses
+template <class F>
+PZ_DEV void for_strided(const float* __restrict__ x, int first, int stride, int n, F f) {
+  int c = first;
+  for (; static_cast<int64_t>(c) + static_cast<int64_t>(kSampleLoads - 1) * stride < n; c += kSampleLoads * stride) {
+    float v[kSampleLoads];
+#pragma unroll
+    for (int k = 0; k < kSampleLoads; ++k) v[k] = x[c + k * stride];
+#pragma unroll
+    for (int k = 0; k < kSampleLoads; ++k) f(c + k * stride, v[k]);
+  }
+  for (; c < n; c += stride) f(c, x[c]);
+}
+
+struct Weigher {
+  float mx, temperature;
+  uint32_t thr;
+  PZ_DEV float operator()(float l, bool& kept) const {
+    kept = okey(l) >= thr;
+    return kept ? __expf((l - mx) / temperature) : 0.f;
+  }
+};
+
+// x: the row's V fp32 logits (global memory or LDS); urow = row0 + row; key = layer_key(seed, step)
+template <int NT>
+PZ_DEV int sample_row(const float* __restrict__ x, int V, float temperature, int top_k, uint32_t urow, uint32_t key,
+                      SampleScratch& sm) {
+  constexpr int kWaves = NT / kWave;
+  static_assert(NT % kWave == 0 && kWaves <= kSampleMaxWaves && kBins % NT == 0 && kMaxBins % NT == 0, "block shape");
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+
+  // 1. row maximum and the lowest index among the maxima
+  unsigned long long best = 0ull;
+  for_strided(x, tid, NT, V, [&](int c, float l) {
+    const unsigned long long p = (static_cast<unsigned long long>(okey(l)) << 32) | (0xFFFFFFFFu - static_cast<uint32_t>(c));
+    best = p > best ? p : best;
+  });
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long t = __shfl_xor(best, o, kWave);
+    best = t > best ? t : best;
+  }
+  if (lane == 0) sm.best_w[wave] = best;
+  __syncthreads();
+  best = sm.best_w[0];
+#pragma unroll
+  for (int w = 1; w < kWaves; ++w) best = sm.best_w[w] > best ? sm.best_w[w] : best;
+  const uint32_t kmax = static_cast<uint32_t>(best >> 32);
+  const int argmax = static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(best));
+
+  int token = argmax;
+  if (temperature > 0.f) {
+    // 2. the k-th largest key, exactly
+    uint32_t thr = 0u;
+    if (top_k > 0 && top_k < V) {
+      uint32_t prefix = 0u, mask = 0u;
+      int krem = top_k;
+#pragma unroll
+      for (int d = 0; d < kDigits; ++d) {
+        const int shift = d == 0 ? 20 : d == 1 ? 10 : 0, bins = d == 0 ? kMaxBins : kBins, per = bins / NT;
+        for (int b = tid; b < bins; b += NT) sm.hist[b] = 0;
+        __syncthreads();
+        for_strided(x, tid, NT, V, [&](int, float l) {
+          const uint32_t k = okey(l);
+          if ((k & mask) == prefix) atomicAdd(&sm.hist[(k >> shift) & (bins - 1)], 1);
+        });
+        __syncthreads();
+        // thread t owns the `per` bins below bins - t * per, descending: a prefix scan over the threads is
+        // a suffix count over the digits
+        const int top = bins - 1 - tid * per;
+        int mine = 0;
+        for (int j = 0; j < per; ++j) mine += sm.hist[top - j];
+        int incl = scan_incl(mine, lane);
+        if (lane == kWave - 1) sm.wtot[wave] = incl;
+        __syncthreads();
+        for (int w = 0; w < wave; ++w) incl += sm.wtot[w];
+        int run = incl - mine;
+        if (run < krem && krem <= incl) {  // exactly one thread: it holds the digit of the k-th largest
+          for (int j = 0; j < per; ++j) {
+            const int h = sm.hist[top - j];
+            if (run + h >= krem) {
+              sm.sel[0] = top - j;
+              sm.sel[1] = krem - run;
+              break;
+            }
+            run += h;
+          }
+        }
+        __syncthreads();
+        prefix |= static_cast<uint32_t>(sm.sel[0]) << shift;
+        mask |= static_cast<uint32_t>(bins - 1) << shift;
+        krem = sm.sel[1];
+      }
+      thr = prefix;
+    }
+
+    // 3a. segment sums
+    const Weigher weigh{okey_inv(kmax), temperature, thr};
+    const int chunks = (V + kWave - 1) / kWave;
+    const int segch = (chunks + kSegments - 1) / kSegments;
+    // a wave owns kOwn consecutive segments and walks them side by side, kStep chunks of each per round
+    // (kSampleLoads loads in flight); every (segment, lane) sum still adds its chunks in chunk order
+    constexpr int kOwn = kSegments / kWaves, kStep = kSampleLoads / kOwn;
+    static_assert(kOwn * kWaves == kSegments && kStep * kOwn == kSampleLoads, "segments per wave");
+    int lastk = -1;
+    float p[kOwn];
+#pragma unroll
+    for (int k = 0; k < kOwn; ++k) p[k] = 0.f;
+    for (int i0 = 0; i0 < segch; i0 += kStep) {
+      float l[kOwn][kStep];
+      int col[kOwn][kStep];  // -1: no such column
+#pragma unroll
+      for (int k = 0; k < kOwn; ++k)
+#pragma unroll
+        for (int j = 0; j < kStep; ++j) {
+          const int64_t c = (static_cast<int64_t>(wave * kOwn + k) * segch + i0 + j) * kWave + lane;
+          col[k][j] = i0 + j < segch && c < V ? static_cast<int>(c) : -1;
+          l[k][j] = col[k][j] >= 0 ? x[col[k][j]] : 0.f;
+        }
+#pragma unroll
+      for (int k = 0; k < kOwn; ++k)
+#pragma unroll
+        for (int j = 0; j < kStep; ++j) {
+          bool kept = false;
+          const float w = col[k][j] >= 0 ? weigh(l[k][j], kept) : 0.f;
+          p[k] += w;  // (+ 0 where there is no column: exact)
+          if (kept) lastk = max(lastk, col[k][j]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kOwn; ++k) {
+      const float total = wave_sum(p[k]);
+      if (lane == 0) sm.segsum[wave * kOwn + k] = total;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lastk = max(lastk, __shfl_xor(lastk, o, kWave));
+    if (lane == 0) sm.lastk_w[wave] = lastk;
+    __syncthreads();
+    if (wave == 0) {  // (no barrier below)
+      // 3b. segment prefixes and the draw
+      const float P = scan_incl(sm.segsum[lane], lane);
+      const float S = __shfl(P, kWave - 1, kWave);
+      const float u = static_cast<float>(mix32(urow ^ key) >> 8) * 0x1p-24f;
+      const float target = u * S;
+      token = sm.lastk_w[0];  // the last kept column: where a walk that runs off the row ends
+#pragma unroll
+      for (int w = 1; w < kWaves; ++w) token = max(token, sm.lastk_w[w]);
+      if (token < 0) token = argmax;  // (a row of NaNs)
+      const unsigned long long over = __ballot(P > target);
+      if (over != 0ull) {
+        // 3c. the walk (the next chunk's logits are loaded before this chunk's scan)
+        const int s = __ffsll(over) - 1;
+        float R = __shfl(P, s > 0 ? s - 1 : 0, kWave);
+        if (s == 0) R = 0.f;
+        int ch = s * segch;
+        float l = ch * kWave + lane < V ? x[ch * kWave + lane] : 0.f;
+        for (; ch < chunks; ++ch) {
+          const int c = ch * kWave + lane;
+          const float lnext = ch + 1 < chunks && c + kWave < V ? x[c + kWave] : 0.f;
+          bool kept = false;
+          const float w = c < V ? weigh(l, kept) : 0.f;
+          kept = kept && c < V;
+          const float incl = scan_incl(w, lane);
+          const unsigned long long hit = __ballot(kept && R + incl > target);
+          if (hit != 0ull) {
+            token = ch * kWave + __ffsll(hit) - 1;
+            break;
+          }
+          R += __shfl(incl, kWave - 1, kWave);
+          l = lnext;
+        }
+      }
+    }
+  }
+  return token;
+}
+
+}  // namespace pz

@@ -55,6 +55,18 @@ window ``seq[:, s : s + L]`` — nothing is shifted in place, ``embedding_fwd`` 
 of the view, its id check is skipped because the ids come from the sampling kernel — and one
 ``PF.sample_rows`` launch (csrc/sample.hip) draws ``seq[:, L + s]`` from the fp32 logits. No host
 read happens inside the loop; the caller downloads ``seq[:, L:]`` once.
+
+One-launch generation, :meth:`FusedPredictor.generate_resident` (``generate(loop="resident")`` of the
+model): for models whose parameters fit in one workgroup's LDS (:mod:`.resident` plans the layout
+within 160 KiB, once per predictor; at most 8192 classes), ``PF.generate_resident``
+(csrc/generate_resident.hip) is the whole request. One workgroup per row copies the parameters into
+LDS, keeps the window on chip and per token runs embedding, the stages and the sampler
+(csrc/sample_core.h, the code of ``sample_rows``) between barriers; only the token store leaves the
+CU. The weights are the predictor's compute-dtype copies (``weights="fp8"``: the dequantised bf16
+copies, which are the e4m3 path's function exactly), the batchnorm running statistics are converted
+per call. The tokens are those ``PF.sample_rows`` draws from the kernel's own logits, which differ
+from the per-token loop's by fp32 summation order only. It is opt-in: a model that does not fit
+raises ``ValueError`` with the planner's reason, never a fall-back to the loop.
 """
 from __future__ import annotations
 
@@ -63,6 +75,7 @@ from torch import Tensor
 
 from ..ops import functional as PF
 from ..ops import native
+from .resident import RESIDENT_LDS_BYTES, describe_stages, resident_plan
 from .trainer import UnsupportedModel, compile_stages
 
 SKINNY_BELOW = 64  # rows from which the tiled GEMMs (M >= 64 on the matrix cores) take over
@@ -92,6 +105,7 @@ class FusedPredictor:
         self.weights8: dict[int, tuple[Tensor, Tensor]] = {}
         self.weights_deq: dict[int, Tensor] = {}
         self._w8_ok: dict[int, bool] = {}
+        self._resident = None  # the one-launch generation plan (or the reason there is none), made on first need
         gemms = [st for st in self.stages if st.kind == "gemm"]
         self.last_gemm = gemms[-1].index if gemms else -1
         with torch.no_grad():
@@ -290,5 +304,66 @@ class FusedPredictor:
                            stop_token=stop_token)
         return seq[:, length:]
 
+    # ------------------------------------------------------------------------------------
+    # one-launch generation (csrc/generate_resident.hip)
+    # ------------------------------------------------------------------------------------
+    def resident_plan(self, budget: int = RESIDENT_LDS_BYTES):
+        """The LDS plan of this model (:func:`.resident.resident_plan`) or the reason it has none; the
+        default-budget answer is made once and kept."""
+        if budget != RESIDENT_LDS_BYTES:
+            return resident_plan(describe_stages(self.stages), self.compute, self.context_length, budget, head=self.head)
+        if self._resident is None:
+            self._resident = resident_plan(describe_stages(self.stages), self.compute, self.context_length, head=self.head)
+        return self._resident
 
-__all__ = ["FusedPredictor", "UnsupportedModel", "SKINNY_BELOW"]
+    def resident_params(self, plan, fp8: bool = False) -> list[Tensor]:
+        """The tensors ``plan.params`` names, in its order: the table, per linear stage the compute-dtype
+        weights (the dequantised e4m3 copies for ``fp8``) and the bias, per batchnorm stage gain, bias and
+        the layer's running statistics as they are now, in fp32."""
+        out = []
+        for index, role in plan.params:
+            st = self.stages[index]
+            if role == "weights" and st.kind == "gemm":
+                out.append((self._dequantised(index) if fp8 else self.weights[index]).contiguous())
+            elif role in ("table", "weights", "gain"):
+                out.append(self.store.view(st.seg_w).contiguous())
+            elif role == "bias":
+                out.append(self.store.view(st.seg_b).contiguous())
+            else:  # not in the store: converted per call, as _batchnorm does
+                stat = st.layer.mean if role == "mean" else st.layer.variance
+                out.append(stat.detach().reshape(-1).to(device=self.dev, dtype=torch.float32).contiguous())
+        return out
+
+    @torch.no_grad()
+    def generate_resident(self, context: Tensor, max_new_tokens: int, temperature: float = 1.0, top_k: int | None = None,
+                          seed: tuple[int, int] = (0, 0), stop_token: int | None = None, weights: str | None = None,
+                          logits_out: Tensor | None = None) -> Tensor:
+        """:meth:`generate` as ONE launch: every row's workgroup keeps the model in LDS and loops over the
+        tokens itself. Same arguments, same rule, same random numbers; the logits differ from the
+        per-token loop's by fp32 summation order only. ``logits_out`` (fp32 ``[rows, steps, V]``, zeroed
+        by the caller) receives each step's logits. ValueError with the planner's reason for a model
+        that does not fit."""
+        fp8 = self._want_fp8(weights)
+        plan = self.resident_plan()
+        if isinstance(plan, str):
+            raise ValueError(plan)
+        length, steps = self.context_length, int(max_new_tokens)
+        context = torch.as_tensor(context)
+        if context.dim() != 2 or context.shape[1] != length or context.is_floating_point():
+            raise ValueError(f"context must be an int tensor [rows, {length}], got {tuple(context.shape)} {context.dtype}")
+        if steps < 1:
+            raise ValueError(f"max_new_tokens must be >= 1, got {max_new_tokens}")
+        rows = context.shape[0]
+        seq = torch.empty(rows, length + steps, device=self.dev, dtype=torch.int64)
+        seq[:, :length] = context.to(device=self.dev, dtype=torch.int64)
+        if rows == 0:
+            return seq[:, length:]
+        vocab = self.store.view(self.stages[0].seg_w).shape[0]
+        PF.check_index_range(seq[:, :length].reshape(-1), -vocab, vocab, "index", vocab)
+        done = torch.zeros(rows, device=self.dev, dtype=torch.int32)
+        PF.generate_resident(seq, done, self.resident_params(plan, fp8), plan.ints, steps, seed=seed,
+                             temperature=temperature, top_k=top_k, stop_token=stop_token, logits_out=logits_out)
+        return seq[:, length:]
+
+
+__all__ = ["FusedPredictor", "UnsupportedModel", "SKINNY_BELOW", "resident_plan", "RESIDENT_LDS_BYTES"]

@@ -370,7 +370,7 @@ class NeuralNetworkModel(MultiLayerPerceptron):
 
     def generate(self, context: list, max_new_tokens: int, temperature: float = 1.0, top_k: int | None = None,
                  seed: int | None = None, stop_token: int | None = None, pad_token: int = 0,
-                 weights: str | None = None) -> dict:
+                 weights: str | None = None, loop: str | None = None) -> dict:
         """Sample ``max_new_tokens`` ids after ``context`` from a next-token model (embedding first,
         softmax head): ``{"tokens": [[...], ...], "seed": int}``, one row per context row.
 
@@ -387,8 +387,20 @@ class NeuralNetworkModel(MultiLayerPerceptron):
         (:meth:`..engine.predictor.FusedPredictor.generate`: the forward kernels plus one sampling
         launch per token, one download at the end). CPU models, the reference runtime and models
         without a predictor run the layer loop under ``no_grad`` with the same rule and the same
-        random numbers. ``weights="fp8"`` as in :meth:`predict`."""
+        random numbers. ``weights="fp8"`` as in :meth:`predict`.
+
+        ``loop="resident"`` opts into the one-launch form
+        (:meth:`..engine.predictor.FusedPredictor.generate_resident`): the model's parameters are
+        copied into every row's workgroup LDS and the token loop runs inside one kernel. It needs a GPU
+        model with a fused predictor whose parameters fit (160 KiB of LDS, at most 8192 classes);
+        anything else raises ``ValueError`` with the reason — there is no silent fall-back to the
+        per-token loop. ``None`` is the per-token loop."""
         from ..ops import functional as PF
+        if loop is not None:
+            if loop != "resident":
+                raise ValueError(f"unknown loop {loop!r}: None (one sampling launch per token) or 'resident'")
+            if not self.on_gpu:
+                raise ValueError("loop='resident' needs a model on a GPU (the resident loop is a HIP kernel)")
         if weights is not None:
             if weights != "fp8":
                 raise ValueError(f"unknown weights {weights!r}: None (the model's own precision) or 'fp8'")
@@ -428,9 +440,17 @@ class NeuralNetworkModel(MultiLayerPerceptron):
             if weights is not None and predictor is None:
                 raise ValueError(f"weights='fp8' is not available for model {self.model_id}: "
                                  f"{getattr(self, '_predictor_reason', 'no fused predictor')}")
+            if loop is not None:
+                reason = (getattr(self, "_predictor_reason", "no fused predictor") if predictor is None
+                          else predictor.resident_plan())
+                if isinstance(reason, str):
+                    raise ValueError(f"loop='resident' is not available for model {self.model_id}: {reason}")
             for layer in self.layers:
                 layer.training = False
-            if predictor is not None:
+            if loop is not None:
+                tokens = predictor.generate_resident(ids, max_new_tokens, temperature=float(temperature), top_k=top_k,
+                                                     seed=key, stop_token=stop_token, weights=weights).tolist()
+            elif predictor is not None:
                 tokens = predictor.generate(ids, max_new_tokens, temperature=float(temperature), top_k=top_k, seed=key,
                                             stop_token=stop_token, weights=weights).tolist()
             else:

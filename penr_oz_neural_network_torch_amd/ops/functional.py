@@ -484,6 +484,20 @@ def sample_rows(logits: Tensor, seq: Tensor, done: Tensor, pos: int, *, seed: tu
                        -1 if stop_token is None else int(stop_token), int(row0))
 
 
+def generate_resident(seq: Tensor, done: Tensor, params: list[Tensor], plan: list[int], steps: int, *,
+                      seed: tuple[int, int], temperature: float = 1.0, top_k: int | None = None,
+                      stop_token: int | None = None, row0: int = 0, logits_out: Tensor | None = None) -> None:
+    """A whole generation request in one launch (csrc/generate_resident.hip): one workgroup per row of
+    ``seq`` (int64 ``[rows, L + steps]``, the context in its first ``L`` columns) copies ``params`` into
+    LDS as ``plan`` (:func:`..engine.resident.resident_plan`) lays them out, then per step runs the
+    model on the last ``L`` ids and draws ``seq[:, L + s]`` by the rule and with the random numbers of
+    :func:`sample_rows` at ``step=s``. ``logits_out`` (fp32 ``[rows, steps, V]``) receives each step's
+    logits. The binding refuses a plan that does not fit the tensors or the device."""
+    _ops().generate_resident(seq, done, list(params), [int(v) for v in plan], int(steps), float(temperature),
+                             int(top_k or 0), int(seed[0]) & _M32, int(seed[1]) & _M32,
+                             -1 if stop_token is None else int(stop_token), int(row0), logits_out)
+
+
 def check_index_range(idx: Tensor, lo: int, hi: int, what: str, size: int | None = None) -> None:
     """Raise IndexError (as ATen / Python indexing do) unless every id is in ``[lo, hi)``.
     The HIP kernels never read outside their tables either way, but a bad id must surface as an
@@ -682,4 +696,4 @@ def tensor_summary(t: Tensor, algo: str | None, bins: int) -> dict:
 __all__ = ["gemm", "gemm_path", "gemm_last_kernel", "gemm_skinny", "gemm_skinny_eligible", "gemm_skinny_w8", "gemm_skinny_w8_eligible",
            "quantize_cols", "quantize_cols_reference", "dequantize_cols", "linear", "activation", "dropout", "softmax", "cross_entropy", "mse_loss",
            "batchnorm", "embedding", "tensor_summary", "epi_spec", "new_seed", "sample_rows", "sample_rows_reference",
-           "sample_uniform"]
+           "sample_uniform", "generate_resident"]
