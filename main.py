@@ -38,6 +38,7 @@ from fastapi.templating import Jinja2Templates
 from pydantic import BaseModel, Field
 
 from neural_net_model import NeuralNetworkModel
+from penr_oz_neural_network_torch_amd.ops.functional import nucleus_args
 from penr_oz_neural_network_torch_amd.parallel import service
 from penr_oz_neural_network_torch_amd.utils import checkpoint as ckpt
 
@@ -130,6 +131,11 @@ class GenerateRequest(ModelRequest):
     max_new_tokens: int = Field(..., description="Tokens to sample per row (1 to 4096).")
     temperature: float = Field(1.0, description="Softmax temperature; 0 is greedy (the most likely token).")
     top_k: int | None = Field(None, description="Sample among the k most likely tokens only (ties at the k-th stay).")
+    top_p: float | None = Field(None, description="Nucleus sampling: sample among the smallest set of most likely tokens "
+                                                  "that holds this share of the probability mass, in (0, 1]; ties with "
+                                                  "the last one admitted stay. Omitted or 1: off.")
+    min_p: float | None = Field(None, description="Drop tokens less than min_p times as likely as the most likely one, "
+                                                  "in [0, 1). Omitted or 0: off.")
     seed: int | None = Field(None, description="64-bit seed naming the random draws; omitted: drawn by the server "
                                                "and returned, so the call can be repeated.")
     stop_token: int | None = Field(None, description="A row ends with its first occurrence of this id (inclusive).")
@@ -314,7 +320,8 @@ def generate_tokens(body: GenerateRequest = Body(..., openapi_examples=GENERATE_
     model_id = body.model_id
     log.info(f"Requesting generation for model {model_id}")
     model = _cached_model(model_id)
-    extra = {} if body.loop is None else {"loop": body.loop}  # (only when asked for, as weights on /predict/)
+    # (only when asked for, as weights on /predict/)
+    extra = {**({} if body.loop is None else {"loop": body.loop}), **nucleus_args(body.top_p, body.min_p)}
     try:
         return model.generate(body.context, body.max_new_tokens, temperature=body.temperature, top_k=body.top_k,
                               seed=body.seed, stop_token=body.stop_token, pad_token=body.pad_token, weights=body.weights,

@@ -725,7 +725,7 @@ void softmax_rows_op(const Tensor& x, const Tensor& y) {
 
 // one token per row into seq[:, pos] (csrc/sample.hip); `key` = layer_key(seed, step) of the host
 void sample_rows_op(const Tensor& logits, const Tensor& seq, const Tensor& done, int64_t pos, double temperature,
-                    int64_t top_k, int64_t key, int64_t stop_token, int64_t row0) {
+                    int64_t top_k, int64_t key, int64_t stop_token, int64_t row0, double top_p, double min_p) {
   check_dev(logits, "logits");
   check_dev(seq, "seq");
   check_dev(done, "done");
@@ -741,6 +741,8 @@ void sample_rows_op(const Tensor& logits, const Tensor& seq, const Tensor& done,
   TORCH_CHECK(pos >= 0 && pos < seq.size(1), "pz::sample_rows: pos ", pos, " is outside seq of length ", seq.size(1));
   TORCH_CHECK(temperature >= 0.0, "pz::sample_rows: temperature must be >= 0 and not NaN, got ", temperature);
   TORCH_CHECK(top_k >= 0, "pz::sample_rows: top_k must be >= 0 (0 = off)");
+  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "pz::sample_rows: top_p must be in (0, 1] (1 = off) and not NaN, got ", top_p);
+  TORCH_CHECK(min_p >= 0.0 && min_p < 1.0, "pz::sample_rows: min_p must be in [0, 1) (0 = off) and not NaN, got ", min_p);
   pz::SampleArgs a{};
   a.logits = logits.data_ptr<float>();
   a.rows = static_cast<int>(rows);
@@ -751,6 +753,8 @@ void sample_rows_op(const Tensor& logits, const Tensor& seq, const Tensor& done,
   a.done = done.data_ptr<int>();
   a.temperature = static_cast<float>(temperature);
   a.top_k = static_cast<int>(std::min<int64_t>(top_k, cols));
+  a.top_p = static_cast<float>(top_p);
+  a.min_p = static_cast<float>(min_p);
   a.key = static_cast<uint32_t>(key);
   a.row0 = static_cast<uint32_t>(row0);
   a.stop_token = stop_token;
@@ -762,13 +766,15 @@ void sample_rows_op(const Tensor& logits, const Tensor& seq, const Tensor& done,
 // access is refused here: the kernel trusts every number it is handed.
 void generate_resident_op(const Tensor& seq, const Tensor& done, at::TensorList params, at::IntArrayRef plan, int64_t steps,
                           double temperature, int64_t top_k, int64_t seed_lo, int64_t seed_hi, int64_t stop_token,
-                          int64_t row0, const optional<Tensor>& logits_out) {
+                          int64_t row0, const optional<Tensor>& logits_out, double top_p, double min_p) {
   const char* who = "pz::generate_resident: ";
   check_dev(seq, "seq");
   check_dev(done, "done");
   TORCH_CHECK(steps >= 1 && steps <= pz::kResMaxSteps, who, "steps must be in [1, ", pz::kResMaxSteps, "], got ", steps);
   TORCH_CHECK(temperature >= 0.0, who, "temperature must be >= 0 and not NaN, got ", temperature);
   TORCH_CHECK(top_k >= 0, who, "top_k must be >= 0 (0 = off)");
+  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, who, "top_p must be in (0, 1] (1 = off) and not NaN, got ", top_p);
+  TORCH_CHECK(min_p >= 0.0 && min_p < 1.0, who, "min_p must be in [0, 1) (0 = off) and not NaN, got ", min_p);
   TORCH_CHECK(static_cast<int64_t>(plan.size()) >= pz::kResHead && static_cast<int64_t>(plan.size()) <= pz::kResPlanMax,
               who, "plan of ", plan.size(), " ints");
   for (const int64_t v : plan)
@@ -889,6 +895,8 @@ void generate_resident_op(const Tensor& seq, const Tensor& done, at::TensorList 
   a.steps = static_cast<int>(steps);
   a.temperature = static_cast<float>(temperature);
   a.top_k = static_cast<int>(std::min<int64_t>(top_k, V));
+  a.top_p = static_cast<float>(top_p);
+  a.min_p = static_cast<float>(min_p);
   a.seed_lo = static_cast<uint32_t>(seed_lo);
   a.seed_hi = static_cast<uint32_t>(seed_hi);
   a.row0 = static_cast<uint32_t>(row0);
@@ -1433,9 +1441,10 @@ TORCH_LIBRARY(pz, m) {
         "float grad_scale, Tensor(c!)? colsum, int[] epi_i, float[] epi_f, int idx_ld) -> ()");
   m.def("softmax_rows(Tensor x, Tensor(a!) y) -> ()");
   m.def("sample_rows(Tensor logits, Tensor(a!) seq, Tensor(b!) done, int pos, float temperature, int top_k, int key, "
-        "int stop_token=-1, int row0=0) -> ()");
+        "int stop_token=-1, int row0=0, float top_p=1.0, float min_p=0.0) -> ()");
   m.def("generate_resident(Tensor(a!) seq, Tensor(b!) done, Tensor[] params, int[] plan, int steps, float temperature, "
-        "int top_k, int seed_lo, int seed_hi, int stop_token=-1, int row0=0, Tensor(c!)? logits_out=None) -> ()");
+        "int top_k, int seed_lo, int seed_hi, int stop_token=-1, int row0=0, Tensor(c!)? logits_out=None, float top_p=1.0, "
+        "float min_p=0.0) -> ()");
   m.def("softmax_bwd(Tensor g, Tensor y, Tensor(a!) dx) -> ()");
   m.def("colsum(Tensor x, Tensor(a!) out) -> ()");
   m.def("gather_rows(Tensor data, Tensor? indices, int seed_lo, int seed_hi, Tensor(a!) out, int rows_valid, "

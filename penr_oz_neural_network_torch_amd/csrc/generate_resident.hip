@@ -35,11 +35,19 @@
 // does not run are left untouched).
 //
 // Barriers per token: 1 (embedding) + 2 per split linear stage (1 unsplit) + 1 per batchnorm + the
-// sampler's (1 greedy, 2 sampling, + 12 with top-k) + 1 after the token.
+// sampler's (1 greedy, 2 sampling, + 12 with top-k, + 12 with top-p) + 1 after the token.
 //
+// Each dtype is built twice: <T, false> for requests without top-p / min-p (sample_row's form that
+// ignores them: the instructions and registers of the kernel before those options existed) and
+// <T, true> for requests with either. The duplication buys the option-free request its old cost: one
+// kernel with a run-time branch measured 2.6 % more per token without the options (206 instead of
+// 168 VGPRs, the min-p compare in every weight), and a request with them gives up a third of the
+// occupancy (2 instead of 3 waves/SIMD) only where it asks for the select.
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
-//   <bf16>  168 VGPRs, 0 AGPRs, 106 SGPRs (65 spilled to VGPR lanes), scratch 0, static LDS 0, occupancy 3 waves/SIMD
-//   <fp32>  166 VGPRs, 0 AGPRs, 106 SGPRs (65 spilled to VGPR lanes), scratch 0, static LDS 0, occupancy 3 waves/SIMD
+//   <bf16, false>  168 VGPRs, 0 AGPRs, 106 SGPRs (63 spilled to VGPR lanes), scratch 0, static LDS 0, occupancy 3 waves/SIMD
+//   <fp32, false>  166 VGPRs, 0 AGPRs, 106 SGPRs (65 spilled to VGPR lanes), scratch 0, static LDS 0, occupancy 3 waves/SIMD
+//   <bf16, true>   206 VGPRs, 0 AGPRs, 106 SGPRs (80 spilled to VGPR lanes), scratch 0, static LDS 0, occupancy 2 waves/SIMD
+//   <fp32, true>   204 VGPRs, 0 AGPRs, 106 SGPRs (80 spilled to VGPR lanes), scratch 0, static LDS 0, occupancy 2 waves/SIMD
 // Dynamic LDS = the plan's total: 28,608 B (bf16) / 36,160 B (fp32) for the character model
 // [27, 10, 30, 64, 27], so registers (3 workgroups per CU), not LDS, bound its residency; one
 // workgroup per CU once a plan passes 80 KiB.
@@ -60,7 +68,8 @@ PZ_DEV void copy_elems(char* dst, const void* src, int numel) {
   for (int i = threadIdx.x; i < numel; i += kNT) d[i] = s[i];
 }
 
-template <typename T>
+// kNucleus: the request has top_p < 1 or min_p > 0 (sample_core.h)
+template <typename T, bool kNucleus>
 __global__ void __launch_bounds__(kNT) generate_resident_kernel(ResidentArgs a) {
   extern __shared__ __attribute__((aligned(16))) char res_smem[];
   const int tid = threadIdx.x;
@@ -200,7 +209,7 @@ __global__ void __launch_bounds__(kNT) generate_resident_kernel(ResidentArgs a) 
 
     // ---- the token
     const uint32_t key = mix32(a.seed_lo ^ mix32(a.seed_hi + 0x9E3779B9u * (static_cast<uint32_t>(s) + 1u)));
-    const int token = sample_row<kNT>(logits, V, a.temperature, a.top_k, a.row0 + static_cast<uint32_t>(row), key, sm);
+    const int token = sample_row<kNT, kNucleus>(logits, V, a.temperature, a.top_k, a.top_p, a.min_p, a.row0 + static_cast<uint32_t>(row), key, sm);
     if (tid == 0) {
       seq[L + s] = token;
       win[s % L] = token;
@@ -216,9 +225,9 @@ __global__ void __launch_bounds__(kNT) generate_resident_kernel(ResidentArgs a) 
   }
 }
 
-template <typename T>
+template <typename T, bool kNucleus>
 hipError_t launch(const ResidentArgs& a, hipStream_t s) {
-  auto kern = generate_resident_kernel<T>;
+  auto kern = generate_resident_kernel<T, kNucleus>;
   static int attr_bytes = 0;  // the largest dynamic LDS size this kernel was granted
   const int lds = a.plan[RH_TOTAL];
   if (lds > attr_bytes) {
@@ -235,17 +244,20 @@ hipError_t launch(const ResidentArgs& a, hipStream_t s) {
 int generate_resident_static_lds() {
   hipFuncAttributes fa{};
   size_t most = 0;
-  if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(generate_resident_kernel<uint16_t>)) == hipSuccess)
-    most = fa.sharedSizeBytes;
-  if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(generate_resident_kernel<float>)) == hipSuccess)
-    most = fa.sharedSizeBytes > most ? fa.sharedSizeBytes : most;
+  const void* kernels[] = {reinterpret_cast<const void*>(generate_resident_kernel<uint16_t, false>),
+                           reinterpret_cast<const void*>(generate_resident_kernel<uint16_t, true>),
+                           reinterpret_cast<const void*>(generate_resident_kernel<float, false>),
+                           reinterpret_cast<const void*>(generate_resident_kernel<float, true>)};
+  for (const void* k : kernels)
+    if (hipFuncGetAttributes(&fa, k) == hipSuccess) most = fa.sharedSizeBytes > most ? fa.sharedSizeBytes : most;
   return static_cast<int>(most);
 }
 
 hipError_t generate_resident(const ResidentArgs& a, hipStream_t s) {
   if (a.rows <= 0) return hipSuccess;
   if (a.steps < 1 || a.steps > kResMaxSteps || a.plan[RH_MAGIC] != kResMagic) return hipErrorInvalidValue;
-  return a.plan[RH_ESIZE] == 2 ? launch<uint16_t>(a, s) : launch<float>(a, s);
+  if (a.top_p < 1.f || a.min_p > 0.f) return a.plan[RH_ESIZE] == 2 ? launch<uint16_t, true>(a, s) : launch<float, true>(a, s);
+  return a.plan[RH_ESIZE] == 2 ? launch<uint16_t, false>(a, s) : launch<float, false>(a, s);
 }
 
 }  // namespace pz

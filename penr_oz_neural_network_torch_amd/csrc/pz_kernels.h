@@ -106,7 +106,7 @@ hipError_t xent_head(const XentArgs& a, hipStream_t s);
 hipError_t mse_head(const MseArgs& a, hipStream_t s);
 hipError_t softmax_rows(const void* x, void* y, int dtype, int rows, int cols, hipStream_t s);
 hipError_t softmax_bwd(const void* g, const void* y, void* dx, int dtype, int rows, int cols, hipStream_t s);
-// one token per row of fp32 logits: greedy / temperature / top-k, counter-based uniform (sample.hip)
+// one token per row of fp32 logits: greedy / temperature / top-k / min-p / top-p, counter-based uniform (sample.hip)
 constexpr int kSampleMaxCols = 1 << 30;
 struct SampleArgs {
   const float* logits;  // [rows][cols]
@@ -116,6 +116,8 @@ struct SampleArgs {
   int* done;            // [rows]: set when a row draws stop_token; a set row writes stop_token
   float temperature;    // 0 = greedy
   int top_k;            // 0 = off
+  float top_p;          // nucleus mass in (0, 1]; >= 1 = off
+  float min_p;          // keep w >= min_p * (the maximum's weight, 1); 0 = off
   uint32_t key;         // u = (mix32((row0 + r) ^ key) >> 8) * 2^-24
   uint32_t row0;
   int64_t stop_token;   // -1 = none
@@ -148,6 +150,7 @@ struct ResidentArgs {
   int rows, steps;
   float temperature;
   int top_k;
+  float top_p, min_p;  // as SampleArgs
   uint32_t seed_lo, seed_hi, row0;
   int64_t stop_token;
 };

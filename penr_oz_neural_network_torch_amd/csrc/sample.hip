@@ -1,6 +1,6 @@
 // pz::sample_rows — draw one token per row from fp32 logits, on the device: the head of the
 // generation loop (engine/predictor.py: FusedPredictor.generate). Greedy (temperature 0) or
-// temperature / top-k sampling by inverse CDF with a counter-based uniform, so a (seed, row, step)
+// temperature / top-k / min-p / top-p (nucleus) sampling by inverse CDF with a counter-based uniform, so a (seed, row, step)
 // names its draw and the host can reproduce it (ops/functional.py: sample_uniform,
 // sample_rows_reference).
 //
@@ -18,6 +18,11 @@
 //     logits of one octave over 8 bins, which keeps same-address LDS atomics short). Integer
 //     arithmetic only: the k-th largest key comes out exactly, columns with key >= it are kept
 //     (ties at the threshold all stay).
+//  2b. min-p (0 < min_p < 1) drops the kept columns with w_c < min_p; top-p (0 < top_p < 1) then keeps
+//     the columns whose strictly-more-likely columns hold less than top_p of the mass that is left:
+//     the same radix select with mass where top-k counts columns (digits of 11, 11 and 10 bits, 64-bit
+//     integer LDS adds of floor(w_c * 2^32): no float atomics, the same bits every time; sample_core.h:
+//     nucleus_key). Ties at the threshold all stay, the maximum always stays.
 //  3. weights w_c = exp((l_c - max) / T) on kept columns, 0 elsewhere, recomputed where needed (the
 //     same instructions give the same bits). The row is cut into chunks of 64 consecutive columns
 //     and into 64 segments of `segch` = ceil(chunks / 64) consecutive chunks.
@@ -42,6 +47,13 @@
 // A row's token depends on its logits, row0 + row, key and the scalars only: not on the row count.
 // Loads are 4-byte and coalesced, issued kSampleLoads at a time before their use (a row is read by one
 // workgroup, so it is the loads in flight, not bandwidth, that set the time of a pass).
+//
+// Every width is built twice: <NT, false> for calls without top-p / min-p (the instructions of the
+// kernel before those options existed) and <NT, true> for calls with either: a call without the
+// options must cost what it cost before, and one kernel with a run-time branch measured 0.2 us more
+// at V = 4096. Resources (hipcc -O3
+// --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage), all with 16,912 B of LDS and no scratch:
+//   <256, false> 92 VGPRs   <256, true> 90 VGPRs   <1024, false> 78 VGPRs   <1024, true> 81 VGPRs
 #include "sample_core.h"
 
 namespace pz {
@@ -49,7 +61,8 @@ namespace {
 
 constexpr int kWideFrom = kSampleNarrowCols;  // columns beyond which a row gets 16 waves instead of 4
 
-template <int NT>
+// kNucleus: the call has top_p < 1 or min_p > 0 (sample_core.h)
+template <int NT, bool kNucleus>
 __global__ void __launch_bounds__(NT) sample_rows_kernel(SampleArgs a) {
   __shared__ SampleScratch sm;
   const int tid = threadIdx.x;
@@ -60,7 +73,7 @@ __global__ void __launch_bounds__(NT) sample_rows_kernel(SampleArgs a) {
     return;
   }
   const float* __restrict__ x = a.logits + static_cast<int64_t>(row) * a.cols;
-  const int token = sample_row<NT>(x, a.cols, a.temperature, a.top_k, a.row0 + static_cast<uint32_t>(row), a.key, sm);
+  const int token = sample_row<NT, kNucleus>(x, a.cols, a.temperature, a.top_k, a.top_p, a.min_p, a.row0 + static_cast<uint32_t>(row), a.key, sm);
   if (tid == 0) {
     *out = token;
     if (token == a.stop_token) a.done[row] = 1;
@@ -73,10 +86,18 @@ hipError_t sample_rows(const SampleArgs& a, hipStream_t s) {
   if (a.rows <= 0) return hipSuccess;
   if (a.cols <= 0 || a.cols > kSampleMaxCols) return hipErrorInvalidValue;
   const dim3 grid(static_cast<unsigned>(a.rows));
-  if (a.cols > kWideFrom)
-    hipLaunchKernelGGL(sample_rows_kernel<1024>, grid, dim3(1024), 0, s, a);
-  else
-    hipLaunchKernelGGL(sample_rows_kernel<256>, grid, dim3(256), 0, s, a);
+  const bool nucleus = a.top_p < 1.f || a.min_p > 0.f;
+  if (a.cols > kWideFrom) {
+    if (nucleus)
+      hipLaunchKernelGGL((sample_rows_kernel<1024, true>), grid, dim3(1024), 0, s, a);
+    else
+      hipLaunchKernelGGL((sample_rows_kernel<1024, false>), grid, dim3(1024), 0, s, a);
+  } else {
+    if (nucleus)
+      hipLaunchKernelGGL((sample_rows_kernel<256, true>), grid, dim3(256), 0, s, a);
+    else
+      hipLaunchKernelGGL((sample_rows_kernel<256, false>), grid, dim3(256), 0, s, a);
+  }
   return hipGetLastError();
 }
 

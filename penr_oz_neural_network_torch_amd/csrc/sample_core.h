@@ -1,5 +1,5 @@
 // pz::sample_row — steps 1-3c of the sampling rule described in sample.hip (row maximum, exact top-k
-// threshold, segment sums, prefix scan and the walk), as one device function shared by
+// threshold, min-p, nucleus threshold, segment sums, prefix scan and the walk), as one device function shared by
 // sample_rows_kernel (logits in global memory, one call per launch) and generate_resident_kernel
 // (logits in LDS, one call per token of a loop). One code, one set of instructions: the same logits,
 // scalars and (row, key) give the same token in both.
@@ -22,17 +22,29 @@ constexpr int kSampleLoads = 16;   // loads in flight per thread
 constexpr int kDigits = 3;         // key digits from the top: 12, 10 and 10 bits
 constexpr int kMaxBins = 1 << 12;
 constexpr int kBins = 1 << 10;
+constexpr int kMassBins = 1 << 11;  // 64-bit bins in hist; nucleus digits from the top: 11, 11 and 10 bits
 
-// the LDS a workgroup needs for one row (16.5 KiB), wherever the kernel keeps it
+// the LDS a workgroup needs for one row (16.5 KiB), wherever the kernel keeps it. The nucleus select
+// (64-bit masses) runs after the maximum and the top-k select are done with their words and re-uses them.
 struct alignas(16) SampleScratch {
-  unsigned long long best_w[kSampleMaxWaves];
-  int hist[kMaxBins];
-  int wtot[kSampleMaxWaves];
+  union {
+    unsigned long long best_w[kSampleMaxWaves];
+    unsigned long long wtot64[kSampleMaxWaves];
+  };
+  union {
+    int hist[kMaxBins];
+    unsigned long long hist64[kMassBins];
+  };
+  union {
+    int wtot[kSampleMaxWaves];
+    unsigned long long sel64[2];
+  };
   int sel[2];
   int lastk_w[kSampleMaxWaves];
   float segsum[kSegments];
 };
 static_assert(sizeof(SampleScratch) == kSampleScratchBytes, "pz_kernels.h: kSampleScratchBytes");
+static_assert(sizeof(int) * kMaxBins == sizeof(unsigned long long) * kMassBins, "hist as 64-bit bins");
 
 // order-preserving image of a float: a > b (as floats, -0 == +0) <=> okey(a) > okey(b)
 PZ_DEV uint32_t okey(float x) {
@@ -66,19 +78,95 @@ PZ_DEV void for_strided(const float* __restrict__ x, int first, int stride, int 
   for (; c < n; c += stride) f(c, x[c]);
 }
 
+// kMinP false: the weigher of a call without min-p, with no trace of it in the instructions
+template <bool kMinP>
 struct Weigher {
-  float mx, temperature;
+  float mx, temperature, min_p;
   uint32_t thr;
   PZ_DEV float operator()(float l, bool& kept) const {
     kept = okey(l) >= thr;
-    return kept ? __expf((l - mx) / temperature) : 0.f;
+    const float w = kept ? __expf((l - mx) / temperature) : 0.f;
+    if (kMinP && w < min_p) kept = false;
+    return kept ? w : 0.f;
   }
 };
 
-// x: the row's V fp32 logits (global memory or LDS); urow = row0 + row; key = layer_key(seed, step)
+// 2b. the nucleus threshold: the largest key t such that the kept columns with key >= t hold at least
+// top_p of the kept mass; columns with key >= t stay (ties at t all stay, the maximum always stays).
+// The top-k select with mass where it counts columns: a column weighs m_c = floor(w_c * 2^32) as an
+// integer (w_c <= 1 and V <= 2^30, so a row's total stays under 2^63), the histograms add integers
+// (ds_add_u64: no order enters, so no float atomics and the same bits every time), and the target is
+// ceil(top_p * total) in [1, total], which exactly one thread's bins cross in every digit pass.
+// weigh: the top-k threshold and min_p, nucleus off. Every thread calls it; 4 barriers per digit.
 template <int NT>
-PZ_DEV int sample_row(const float* __restrict__ x, int V, float temperature, int top_k, uint32_t urow, uint32_t key,
-                      SampleScratch& sm) {
+PZ_DEV uint32_t nucleus_key(const float* __restrict__ x, int V, const Weigher<true>& weigh, float top_p, SampleScratch& sm) {
+  constexpr int kWaves = NT / kWave;
+  static_assert(kMassBins % NT == 0, "block shape");
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+  uint32_t prefix = 0u, mask = 0u;
+  unsigned long long rem = 0ull;
+#pragma unroll
+  for (int d = 0; d < kDigits; ++d) {
+    const int shift = d == 0 ? 21 : d == 1 ? 10 : 0, bins = d == 2 ? kBins : kMassBins, per = bins / NT;
+    for (int b = tid; b < bins; b += NT) sm.hist64[b] = 0ull;
+    // a row without mass (all NaN) has no finder: digit 0 and rem 0 then stand through every pass. Only before
+    // the first pass: later passes' readers of sel64 have no barrier between their read and this point.
+    if (d == 0 && tid == 0) sm.sel64[0] = sm.sel64[1] = 0ull;
+    __syncthreads();
+    for_strided(x, tid, NT, V, [&](int, float l) {
+      const uint32_t k = okey(l);
+      if ((k & mask) == prefix) {
+        bool kept = false;
+        const float w = weigh(l, kept);
+        const unsigned long long m = w > 0.f ? static_cast<unsigned long long>(w * 0x1p32f) : 0ull;
+        if (m != 0ull) atomicAdd(&sm.hist64[(k >> shift) & (bins - 1)], m);
+      }
+    });
+    __syncthreads();
+    const int top = bins - 1 - tid * per;  // thread t owns the `per` bins below bins - t * per, descending
+    unsigned long long mine = 0ull;
+    for (int j = 0; j < per; ++j) mine += sm.hist64[top - j];
+    unsigned long long incl = scan_incl(mine, lane);
+    if (lane == kWave - 1) sm.wtot64[wave] = incl;
+    __syncthreads();
+    unsigned long long total = 0ull;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+      const unsigned long long t = sm.wtot64[w];
+      incl += w < wave ? t : 0ull;
+      total += t;
+    }
+    if (d == 0) {
+      const double want = ceil(static_cast<double>(top_p) * static_cast<double>(total));
+      rem = want >= static_cast<double>(total) ? total : static_cast<unsigned long long>(want);
+      rem = rem < 1ull ? 1ull : rem;
+    }
+    unsigned long long run = incl - mine;
+    if (run < rem && rem <= incl) {  // exactly one thread (none when total == 0)
+      for (int j = 0; j < per; ++j) {
+        const unsigned long long h = sm.hist64[top - j];
+        if (run + h >= rem) {
+          sm.sel64[0] = static_cast<unsigned long long>(top - j);
+          sm.sel64[1] = rem - run;
+          break;
+        }
+        run += h;
+      }
+    }
+    __syncthreads();
+    prefix |= static_cast<uint32_t>(sm.sel64[0]) << shift;
+    mask |= static_cast<uint32_t>(bins - 1) << shift;
+    rem = sm.sel64[1];
+  }
+  return prefix;
+}
+
+// x: the row's V fp32 logits (global memory or LDS); urow = row0 + row; key = layer_key(seed, step);
+// top_p >= 1 and min_p == 0: off. kNucleus false ignores both: the kernels instantiate that form for
+// calls without the options, so such a call runs the instructions it ran before the options existed.
+template <int NT, bool kNucleus>
+PZ_DEV int sample_row(const float* __restrict__ x, int V, float temperature, int top_k, float top_p, float min_p,
+                      uint32_t urow, uint32_t key, SampleScratch& sm) {
   constexpr int kWaves = NT / kWave;
   static_assert(NT % kWave == 0 && kWaves <= kSampleMaxWaves && kBins % NT == 0 && kMaxBins % NT == 0, "block shape");
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
@@ -148,8 +236,14 @@ PZ_DEV int sample_row(const float* __restrict__ x, int V, float temperature, int
       thr = prefix;
     }
 
+    // 2b. min-p is a condition of the weigher; the nucleus raises the threshold key (workgroup-uniform)
+    if (kNucleus && top_p < 1.f) {
+      const uint32_t t = nucleus_key<NT>(x, V, Weigher<true>{okey_inv(kmax), temperature, min_p, thr}, top_p, sm);
+      thr = t > thr ? t : thr;
+    }
+
     // 3a. segment sums
-    const Weigher weigh{okey_inv(kmax), temperature, thr};
+    const Weigher<kNucleus> weigh{okey_inv(kmax), temperature, min_p, thr};
     const int chunks = (V + kWave - 1) / kWave;
     const int segch = (chunks + kSegments - 1) / kSegments;
     // a wave owns kOwn consecutive segments and walks them side by side, kStep chunks of each per round

@@ -273,13 +273,16 @@ class FusedPredictor:
 
     @torch.no_grad()
     def generate(self, context: Tensor, max_new_tokens: int, temperature: float = 1.0, top_k: int | None = None,
-                 seed: tuple[int, int] = (0, 0), stop_token: int | None = None, weights: str | None = None) -> Tensor:
+                 seed: tuple[int, int] = (0, 0), stop_token: int | None = None, weights: str | None = None,
+                 top_p: float | None = None, min_p: float | None = None) -> Tensor:
         """``context``: int ids ``[rows, context_length]``. Returns the int64 ``[rows, max_new_tokens]``
         continuation, on the device. One upload, then per token the forward kernels on the window
         ``seq[:, s : s + L]`` and one ``PF.sample_rows`` launch that writes ``seq[:, L + s]``; nothing is
         read back inside the loop. Step ``s`` of row ``r`` draws ``PF.sample_uniform(seed, r, s)``; a row
-        that drew ``stop_token`` repeats it from then on."""
+        that drew ``stop_token`` repeats it from then on. ``top_p`` / ``min_p`` as in
+        :func:`..ops.functional.sample_rows_reference`; they reach the sampler only when set."""
         fp8 = self._want_fp8(weights)
+        extra = PF.nucleus_args(top_p, min_p)
         reason = self.generation_unsupported()
         if reason is not None:
             raise ValueError(reason)
@@ -301,7 +304,7 @@ class FusedPredictor:
         for s in range(steps):
             logits = self._logits(seq[:, s:s + length], fp8, check_ids=False).reshape(rows, width)
             PF.sample_rows(logits, seq, done, length + s, seed=seed, step=s, temperature=temperature, top_k=top_k,
-                           stop_token=stop_token)
+                           stop_token=stop_token, **extra)
         return seq[:, length:]
 
     # ------------------------------------------------------------------------------------
@@ -337,7 +340,8 @@ class FusedPredictor:
     @torch.no_grad()
     def generate_resident(self, context: Tensor, max_new_tokens: int, temperature: float = 1.0, top_k: int | None = None,
                           seed: tuple[int, int] = (0, 0), stop_token: int | None = None, weights: str | None = None,
-                          logits_out: Tensor | None = None) -> Tensor:
+                          logits_out: Tensor | None = None, top_p: float | None = None,
+                          min_p: float | None = None) -> Tensor:
         """:meth:`generate` as ONE launch: every row's workgroup keeps the model in LDS and loops over the
         tokens itself. Same arguments, same rule, same random numbers; the logits differ from the
         per-token loop's by fp32 summation order only. ``logits_out`` (fp32 ``[rows, steps, V]``, zeroed
@@ -362,7 +366,8 @@ class FusedPredictor:
         PF.check_index_range(seq[:, :length].reshape(-1), -vocab, vocab, "index", vocab)
         done = torch.zeros(rows, device=self.dev, dtype=torch.int32)
         PF.generate_resident(seq, done, self.resident_params(plan, fp8), plan.ints, steps, seed=seed,
-                             temperature=temperature, top_k=top_k, stop_token=stop_token, logits_out=logits_out)
+                             temperature=temperature, top_k=top_k, stop_token=stop_token, logits_out=logits_out,
+                             **PF.nucleus_args(top_p, min_p))
         return seq[:, length:]
 
 

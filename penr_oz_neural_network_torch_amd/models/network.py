@@ -370,7 +370,8 @@ class NeuralNetworkModel(MultiLayerPerceptron):
 
     def generate(self, context: list, max_new_tokens: int, temperature: float = 1.0, top_k: int | None = None,
                  seed: int | None = None, stop_token: int | None = None, pad_token: int = 0,
-                 weights: str | None = None, loop: str | None = None) -> dict:
+                 weights: str | None = None, loop: str | None = None, top_p: float | None = None,
+                 min_p: float | None = None) -> dict:
         """Sample ``max_new_tokens`` ids after ``context`` from a next-token model (embedding first,
         softmax head): ``{"tokens": [[...], ...], "seed": int}``, one row per context row.
 
@@ -378,7 +379,9 @@ class NeuralNetworkModel(MultiLayerPerceptron):
         is left-padded with ``pad_token``, a longer one contributes its last ``context_length`` ids.
         Each step feeds the last ``context_length`` ids, takes the logits and draws by the rule of
         :func:`..ops.functional.sample_rows_reference`: ``temperature == 0`` is greedy, ``top_k``
-        keeps the k largest logits (ties included), and row ``r`` draws
+        keeps the k largest logits (ties included), ``min_p`` drops what is less than ``min_p`` times as
+        likely as the most likely token, ``top_p`` keeps the smallest set of most likely tokens that holds
+        ``top_p`` of the remaining mass (nucleus sampling; ties with the last one stay), and row ``r`` draws
         ``PF.sample_uniform((seed & 0xFFFFFFFF, seed >> 32), r, step)`` at step ``step`` — so a seed
         names its output; ``seed=None`` takes 64 bits from ``os.urandom`` and returns them. A row is
         cut after its first ``stop_token`` (inclusive).
@@ -413,6 +416,11 @@ class NeuralNetworkModel(MultiLayerPerceptron):
             raise ValueError(f"temperature must be >= 0, got {temperature!r}")
         if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 1):
             raise ValueError(f"top_k must be an integer >= 1, got {top_k!r}")
+        if top_p is not None and (isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not 0 < top_p <= 1):
+            raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
+        if min_p is not None and (isinstance(min_p, bool) or not isinstance(min_p, (int, float)) or not 0 <= min_p < 1):
+            raise ValueError(f"min_p must be in [0, 1), got {min_p!r}")
+        extra = PF.nucleus_args(top_p, min_p)  # (only when set, as loop)
         if stop_token is not None and (not isinstance(stop_token, int) or not 0 <= stop_token < classes):
             raise ValueError(f"stop_token {stop_token!r} is outside the vocabulary of {classes}")
         if not isinstance(pad_token, int) or not 0 <= pad_token < vocab:
@@ -449,17 +457,17 @@ class NeuralNetworkModel(MultiLayerPerceptron):
                 layer.training = False
             if loop is not None:
                 tokens = predictor.generate_resident(ids, max_new_tokens, temperature=float(temperature), top_k=top_k,
-                                                     seed=key, stop_token=stop_token, weights=weights).tolist()
+                                                     seed=key, stop_token=stop_token, weights=weights, **extra).tolist()
             elif predictor is not None:
                 tokens = predictor.generate(ids, max_new_tokens, temperature=float(temperature), top_k=top_k, seed=key,
-                                            stop_token=stop_token, weights=weights).tolist()
+                                            stop_token=stop_token, weights=weights, **extra).tolist()
             else:
-                tokens = self._generate_layers(ids, max_new_tokens, float(temperature), top_k, key, stop_token)
+                tokens = self._generate_layers(ids, max_new_tokens, float(temperature), top_k, key, stop_token, **extra)
         if stop_token is not None:
             tokens = [row[:row.index(stop_token) + 1] if stop_token in row else row for row in tokens]
         return {"tokens": tokens, "seed": seed}
 
-    def _generate_layers(self, ids: Tensor, steps: int, temperature: float, top_k, key, stop_token) -> list:
+    def _generate_layers(self, ids: Tensor, steps: int, temperature: float, top_k, key, stop_token, **nucleus) -> list:
         """The generation loop through the layers (``_forward`` in eval mode) with the pure-torch sampler."""
         from ..ops import functional as PF
         rows, length = ids.shape
@@ -467,7 +475,7 @@ class NeuralNetworkModel(MultiLayerPerceptron):
         done = torch.zeros(rows, dtype=torch.bool, device=self.device)
         for s in range(steps):
             logits = self._forward(seq[:, s:s + length], None)[0][-2].detach()  # the softmax layer's input
-            token = PF.sample_rows_reference(logits.reshape(rows, -1), key, s, temperature, top_k)
+            token = PF.sample_rows_reference(logits.reshape(rows, -1), key, s, temperature, top_k, **nucleus)
             if stop_token is not None:
                 token = torch.where(done, torch.full_like(token, stop_token), token)
                 done |= token == stop_token

@@ -436,23 +436,41 @@ def _sample_uniforms(seed: tuple[int, int], rows: int, step: int, row0: int, dev
     return (x >> 8).double() * 2.0 ** -24
 
 
+def _check_nucleus(top_p: float | None, min_p: float | None) -> tuple[float, float]:
+    """``(top_p, min_p)`` with the off values ``1.0`` / ``0.0`` for ``None``; ValueError outside
+    ``(0, 1]`` / ``[0, 1)`` (NaN included)."""
+    if top_p is not None and not 0 < top_p <= 1:
+        raise ValueError(f"top_p must be in (0, 1], got {top_p}")
+    if min_p is not None and not 0 <= min_p < 1:
+        raise ValueError(f"min_p must be in [0, 1), got {min_p}")
+    return (1.0 if top_p is None else float(top_p)), (0.0 if min_p is None else float(min_p))
+
+
 def sample_rows_reference(logits: Tensor, seed: tuple[int, int], step: int, temperature: float = 1.0,
-                          top_k: int | None = None, row0: int = 0) -> Tensor:
+                          top_k: int | None = None, row0: int = 0, top_p: float | None = None,
+                          min_p: float | None = None) -> Tensor:
     """The sampling rule of :func:`sample_rows` in pure torch, in fp64, on CPU or GPU tensors:
     ``logits [rows, V]`` (or ``[V]``) -> int64 tokens ``[rows]``. It is the sampler of the runtimes
     without the kernel and the yardstick of the kernel's tests.
 
     * top-k: keep the columns whose logit is ``>=`` the k-th largest of the row (ties all stay);
       ``None`` / ``0`` / ``k >= V`` keep everything;
-    * ``temperature == 0``: the lowest index among the maxima, nothing drawn;
-    * otherwise ``w_c = exp((l_c - max) / T)`` on kept columns (``T`` rounded to fp32, as the kernel
-      receives it), ``u = sample_uniform(seed, row0 + row, step)``, and the token is the smallest
+    * ``temperature == 0``: the lowest index among the maxima, nothing drawn, whatever the options;
+    * ``w_c = exp((l_c - max) / T)`` (``T`` rounded to fp32, as the kernel receives it);
+    * min-p (``0 < min_p < 1``; ``None`` / ``0`` is off) then drops the kept columns with
+      ``w_c < min_p`` — the maximum has ``w = 1`` and stays;
+    * top-p (``0 < top_p < 1``; ``None`` / ``1`` is off) then keeps, of what is left with mass ``S0``,
+      the columns whose strictly-more-likely columns hold less than ``top_p * S0``: the smallest set
+      of most likely columns whose mass reaches ``top_p * S0``, with every column tied with the last
+      one admitted; the most likely column always stays;
+    * the draw: ``u = sample_uniform(seed, row0 + row, step)``, and the token is the smallest
       kept ``c`` whose inclusive prefix sum of ``w`` exceeds ``u * sum(w)`` — the last kept column if
       rounding leaves none."""
     if temperature != temperature or temperature < 0:
         raise ValueError(f"temperature must be >= 0, got {temperature}")
     if top_k is not None and top_k < 0:
         raise ValueError(f"top_k must be >= 0, got {top_k}")
+    top_p, min_p = _check_nucleus(top_p, min_p)
     lg = logits.detach()
     lg = (lg.unsqueeze(0) if lg.dim() == 1 else lg.reshape(-1, lg.shape[-1])).double()
     rows, v = lg.shape
@@ -464,7 +482,22 @@ def sample_rows_reference(logits: Tensor, seed: tuple[int, int], step: int, temp
     if top_k and top_k < v:
         kept = lg >= torch.topk(lg, top_k, dim=-1).values[:, -1:]
     t32 = float(torch.tensor(temperature, dtype=torch.float32))
-    w = torch.where(kept, torch.exp((lg - mx) / t32), torch.zeros_like(lg))
+    w = torch.exp((lg - mx) / t32)
+    if min_p > 0:
+        kept = kept & ~(w < min_p)
+    w = torch.where(kept, w, torch.zeros_like(lg))
+    if top_p < 1:
+        # mass of the kept columns with a strictly larger logit: the exclusive prefix of the weights in
+        # descending logit order, read at the first column of each run of equal logits
+        ls, order = lg.sort(dim=-1, descending=True, stable=True)
+        ws = w.gather(1, order)
+        excl = ws.cumsum(dim=-1) - ws
+        first = torch.ones_like(kept)
+        first[:, 1:] = ls[:, 1:] != ls[:, :-1]
+        above = torch.where(first, excl, torch.zeros_like(excl)).cummax(dim=-1).values
+        stay = above < top_p * ws.sum(dim=-1, keepdim=True)
+        kept = kept & torch.zeros_like(kept).scatter(1, order, stay)
+        w = torch.where(kept, w, torch.zeros_like(lg))
     cdf = w.cumsum(dim=-1)
     target = _sample_uniforms(seed, rows, step, row0, lg.device) * cdf[:, -1]
     first = torch.where(kept & (cdf > target.unsqueeze(1)), idx, v).min(dim=-1).values
@@ -472,21 +505,30 @@ def sample_rows_reference(logits: Tensor, seed: tuple[int, int], step: int, temp
     return torch.where(first < v, first, last_kept)
 
 
+def nucleus_args(top_p: float | None, min_p: float | None) -> dict:
+    """``top_p`` / ``min_p`` as keyword arguments, the set ones only: every layer from ``POST /generate/`` down to
+    the operators passes them on this way, so a call without them reaches the layer below exactly as it did
+    before they existed (an unset one keeps the operator schema's off value)."""
+    return {k: float(v) for k, v in (("top_p", top_p), ("min_p", min_p)) if v is not None}
+
+
 def sample_rows(logits: Tensor, seq: Tensor, done: Tensor, pos: int, *, seed: tuple[int, int], step: int,
                 temperature: float = 1.0, top_k: int | None = None, stop_token: int | None = None,
-                row0: int = 0) -> None:
+                row0: int = 0, top_p: float | None = None, min_p: float | None = None) -> None:
     """One token per row of the fp32 ``logits [rows, V]`` into ``seq[:, pos]`` (int64 ``[rows, length]``),
     by the rule of :func:`sample_rows_reference` with ``u = sample_uniform(seed, row0 + row, step)``
     (csrc/sample.hip; one launch, nothing comes back to the host). ``done`` (int32 ``[rows]``): a row
     whose flag is set writes ``stop_token``; a row that draws ``stop_token`` sets its flag. The call is
-    bit-reproducible and a row's token does not depend on the rows sent with it."""
+    bit-reproducible and a row's token does not depend on the rows sent with it. The binding refuses a
+    ``top_p`` outside ``(0, 1]`` and a ``min_p`` outside ``[0, 1)``."""
     _ops().sample_rows(logits, seq, done, pos, float(temperature), int(top_k or 0), layer_key(seed, step),
-                       -1 if stop_token is None else int(stop_token), int(row0))
+                       -1 if stop_token is None else int(stop_token), int(row0), **nucleus_args(top_p, min_p))
 
 
 def generate_resident(seq: Tensor, done: Tensor, params: list[Tensor], plan: list[int], steps: int, *,
                       seed: tuple[int, int], temperature: float = 1.0, top_k: int | None = None,
-                      stop_token: int | None = None, row0: int = 0, logits_out: Tensor | None = None) -> None:
+                      stop_token: int | None = None, row0: int = 0, logits_out: Tensor | None = None,
+                      top_p: float | None = None, min_p: float | None = None) -> None:
     """A whole generation request in one launch (csrc/generate_resident.hip): one workgroup per row of
     ``seq`` (int64 ``[rows, L + steps]``, the context in its first ``L`` columns) copies ``params`` into
     LDS as ``plan`` (:func:`..engine.resident.resident_plan`) lays them out, then per step runs the
@@ -495,7 +537,8 @@ def generate_resident(seq: Tensor, done: Tensor, params: list[Tensor], plan: lis
     logits. The binding refuses a plan that does not fit the tensors or the device."""
     _ops().generate_resident(seq, done, list(params), [int(v) for v in plan], int(steps), float(temperature),
                              int(top_k or 0), int(seed[0]) & _M32, int(seed[1]) & _M32,
-                             -1 if stop_token is None else int(stop_token), int(row0), logits_out)
+                             -1 if stop_token is None else int(stop_token), int(row0), logits_out,
+                             **nucleus_args(top_p, min_p))
 
 
 def check_index_range(idx: Tensor, lo: int, hi: int, what: str, size: int | None = None) -> None:
@@ -695,5 +738,5 @@ def tensor_summary(t: Tensor, algo: str | None, bins: int) -> dict:
 
 __all__ = ["gemm", "gemm_path", "gemm_last_kernel", "gemm_skinny", "gemm_skinny_eligible", "gemm_skinny_w8", "gemm_skinny_w8_eligible",
            "quantize_cols", "quantize_cols_reference", "dequantize_cols", "linear", "activation", "dropout", "softmax", "cross_entropy", "mse_loss",
-           "batchnorm", "embedding", "tensor_summary", "epi_spec", "new_seed", "sample_rows", "sample_rows_reference",
+           "batchnorm", "embedding", "tensor_summary", "epi_spec", "new_seed", "sample_rows", "sample_rows_reference", "nucleus_args",
            "sample_uniform", "generate_resident"]

@@ -25,7 +25,14 @@ Models (bfloat16, batchnorm statistics from one training-mode forward):
    alone (trains of back-to-back ``PF.generate_resident`` launches) divided by the steps. Runs only
    this section and writes profiles/generate_resident_latency.txt.
 
-Usage: python tools/generate_bench.py [--out profiles/generate_latency.txt] [--quick] [--resident]
+4. ``--top-p``: nucleus sampling. ``pz::sample_rows`` alone as in 2. with ``top_p = 0.9``, alone and
+   with ``top_k = 50``, next to the same launch without it and with ``top_k = 50`` only; then tokens
+   per second of ``model.generate(top_p=0.9)``, per-token and (chars) ``loop="resident"``, against the
+   loop a caller had for top-p before: per token ``model.predict``, then sort, cumulative sum and
+   ``torch.multinomial`` on the host. Runs only this section and writes
+   profiles/sample_top_p_latency.txt.
+
+Usage: python tools/generate_bench.py [--out profiles/generate_latency.txt] [--quick] [--resident | --top-p]
 """
 from __future__ import annotations
 
@@ -112,6 +119,66 @@ def model_throughput(name: str, quick: bool) -> list[str]:
         lines.append(f"{rows:>5} | {statistics.median(rd):>17,.0f} [{_iqr(rd):>8,.0f}] {statistics.median(td) * 1e3:>9.3f} | "
                      f"{statistics.median(rh):>23,.0f} [{_iqr(rh):>8,.0f}] {statistics.median(th) * 1e3:>9.3f} | "
                      f"{statistics.median(rd) / statistics.median(rh):>12.2f}x")
+    return lines + [""]
+
+
+def host_loop_top_p(model, context: list, steps: int, generator: torch.Generator, top_p: float) -> list:
+    """The per-token loop over the public ``predict`` with nucleus sampling on the host."""
+    windows = [list(row) for row in context]
+    out = [[] for _ in context]
+    for _ in range(steps):
+        probs = torch.tensor(model.predict(windows))
+        sp, order = probs.sort(dim=-1, descending=True)
+        sp = sp.masked_fill(sp.cumsum(-1) - sp >= top_p, 0.0)
+        picks = order.gather(1, torch.multinomial(sp, 1, generator=generator))[:, 0].tolist()
+        for row, window, token in zip(out, windows, picks):
+            row.append(token)
+            window.pop(0)
+            window.append(token)
+    return out
+
+
+def top_p_throughput(name: str, quick: bool, top_p: float = 0.9) -> list[str]:
+    model = _build(name)
+    pred = model._fused_predictor()
+    assert pred is not None, "the bench models must go through the fused predictor"
+    resident = not isinstance(pred.resident_plan(), str)
+    length, vocab = model.context_length, MODELS[name][0]
+    lines = [f"== {name} {MODELS[name]} bfloat16, context {length}, {TOKENS} new tokens per row and call, top_p = {top_p}: "
+             "tokens/s, median [interquartile range] ==",
+             f"{'rows':>5} | {'generate(top_p)':>28} {'ms/call':>9} | {'generate(top_p, resident)':>28} {'ms/call':>9} | "
+             f"{'host loop (predict + sort + cumsum)':>36} {'ms/call':>9} | {'loop / host':>11} | {'resident / host':>15}"]
+    g = torch.Generator().manual_seed(2)
+    for rows in ROWS:
+        context = torch.randint(0, vocab, (rows, length), generator=g).tolist()
+        sampler = torch.Generator().manual_seed(3)
+        seeds = iter(range(1, 1 << 30))
+        reps = 5 if quick else 25
+        calls = [lambda: model.generate(context, TOKENS, seed=next(seeds), top_p=top_p),
+                 (lambda: model.generate(context, TOKENS, seed=next(seeds), top_p=top_p, loop="resident")) if resident else None,
+                 lambda: host_loop_top_p(model, context, TOKENS, sampler, top_p)]
+        for _ in range(2):
+            for call in calls:
+                if call is not None:
+                    call()
+        times = [[] for _ in calls]
+        for _ in range(reps):  # alternating; each call ends with its tokens on the host
+            for t, call in zip(times, calls):
+                if call is not None:
+                    t0 = time.perf_counter()
+                    call()
+                    t.append(time.perf_counter() - t0)
+        n = rows * TOKENS
+
+        def cell(t, width):
+            if not t:
+                return f"{'(does not fit in LDS)':>{width + 11}} {'':>9}"
+            r = [n / x for x in t]
+            return f"{statistics.median(r):>{width},.0f} [{_iqr(r):>8,.0f}] {statistics.median(t) * 1e3:>9.3f}"
+
+        med = [statistics.median(t) if t else None for t in times]
+        lines.append(f"{rows:>5} | {cell(times[0], 17)} | {cell(times[1], 17)} | {cell(times[2], 25)} | "
+                     f"{med[2] / med[0]:>10.2f}x | " + (f"{med[2] / med[1]:>14.2f}x" if med[1] else f"{'-':>15}"))
     return lines + [""]
 
 
@@ -206,10 +273,16 @@ def resident_throughput(dtype: str, quick: bool) -> list[str]:
     return lines + [""]
 
 
-def kernel_times(dev, quick: bool) -> list[str]:
+def kernel_times(dev, quick: bool, top_p: bool = False) -> list[str]:
     lines = ["== pz::sample_rows alone: us per launch, device events around trains of back-to-back launches on fixed",
              "   logits, median over the trains [interquartile range]; T = 0.8 ==",
              f"{'V':>6} {'rows':>5} | {'top_k off':>18} | {'top_k = 50':>18} | {'greedy (T = 0)':>18}"]
+    modes = ((0.8, None, {}), (0.8, 50, {}), (0.0, None, {}))
+    if top_p:
+        lines[-1] = (f"{'V':>6} {'rows':>5} | {'options off':>18} | {'top_k = 50':>18} | {'top_p = 0.9':>18} | "
+                     f"{'top_p 0.9, top_k 50':>19} | {'min_p = 0.05':>18}")
+        modes = ((0.8, None, {}), (0.8, 50, {}), (0.8, None, {"top_p": 0.9}), (0.8, 50, {"top_p": 0.9}),
+                 (0.8, None, {"min_p": 0.05}))
     iters, trains = (100, 3) if quick else (1000, 7)
     g = torch.Generator().manual_seed(4)
     for v in (27, 4096, 65536):
@@ -218,9 +291,10 @@ def kernel_times(dev, quick: bool) -> list[str]:
             seq = torch.zeros(rows, 4, device=dev, dtype=torch.int64)
             done = torch.zeros(rows, device=dev, dtype=torch.int32)
             cells = []
-            for temperature, top_k in ((0.8, None), (0.8, 50), (0.0, None)):
+            for temperature, top_k, extra in modes:
                 def launch(i):
-                    PF.sample_rows(logits, seq, done, i & 3, seed=(5, 6), step=i, temperature=temperature, top_k=top_k)
+                    PF.sample_rows(logits, seq, done, i & 3, seed=(5, 6), step=i, temperature=temperature, top_k=top_k,
+                                   **extra)
                 for i in range(10):
                     launch(i)
                 torch.cuda.synchronize()
@@ -245,9 +319,11 @@ def main(argv=None) -> int:
                                                 "with --resident)")
     ap.add_argument("--quick", action="store_true", help="fewer repeats (a rehearsal, not a measurement)")
     ap.add_argument("--resident", action="store_true", help="only section 3: the one-launch form against the device loop")
+    ap.add_argument("--top-p", action="store_true", help="only section 4: nucleus sampling")
     args = ap.parse_args(argv)
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "generate_resident_latency.txt" if args.resident else "generate_latency.txt")
+        args.out = os.path.join(ROOT, "profiles", "sample_top_p_latency.txt" if args.top_p else
+                                "generate_resident_latency.txt" if args.resident else "generate_latency.txt")
     if not torch.cuda.is_available():
         print("generate_bench needs a GPU: nothing was measured", file=sys.stderr)
         return 2
@@ -255,7 +331,11 @@ def main(argv=None) -> int:
     dev = torch.device("cuda:0")
     lines = [f"generate_bench: {torch.cuda.get_device_name(0)}, torch {torch.__version__}"
              f"{' (quick: fewer repeats)' if args.quick else ''}", ""]
-    if args.resident:
+    if args.top_p:
+        lines += kernel_times(dev, args.quick, top_p=True) + [""]
+        for name in MODELS:
+            lines += top_p_throughput(name, args.quick)
+    elif args.resident:
         for dtype in ("bfloat16", "float32"):
             lines += resident_throughput(dtype, args.quick)
     else:
