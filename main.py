@@ -7,6 +7,7 @@ existing clients, its test-suite and the dashboard work unchanged:
     POST /model/        create + serialize            POST /output/       inference (+ cost)
     POST /predict/      batch inference, outputs only (models stay loaded between requests)
     POST /generate/     token sampling from a next-token model (same loaded models as /predict/)
+    POST /score/        log-probabilities, ranks and perplexity of given id sequences (same loaded models)
     PUT  /train/        202, training in background   (409 while that model is training)
     GET  /progress/     progress / avg cost / status  GET /stats/         training diagnostics
     DELETE /model/      204
@@ -145,6 +146,19 @@ class GenerateRequest(ModelRequest):
                                                "on-chip memory (GPU models whose parameters fit in 160 KiB, at most "
                                                "8192 classes; anything else answers 400 with the reason). Omitted: "
                                                "one sampling launch per token.")
+    logprobs: bool | None = Field(None, description="true: the response gains 'logprobs', the log-probability of every "
+                                                    "returned token under the model's own distribution (temperature 1, "
+                                                    "no top-k / top-p / min-p truncation), from one scoring pass after "
+                                                    "the loop. Omitted: nothing extra is computed.")
+
+
+class ScoreRequest(ModelRequest):
+    sequences: list = Field(..., description="One non-empty id list or a batch of non-empty id lists. Every id is scored "
+                                             "given the ids before it (as many as the model's context length; a row is "
+                                             "left-padded with pad_token). At most 1,048,576 ids per request.")
+    pad_token: int = Field(0, description="Id that left-pads every row, as on /generate/.")
+    weights: str | None = Field(None, description="'fp8': weight-only e4m3 copies, as on /predict/.")
+    details: bool = Field(True, description="false: only tokens, nll, perplexity and top1 come back, no per-id lists.")
 
 
 class TrainingRequest(ModelRequest):
@@ -321,12 +335,40 @@ def generate_tokens(body: GenerateRequest = Body(..., openapi_examples=GENERATE_
     log.info(f"Requesting generation for model {model_id}")
     model = _cached_model(model_id)
     # (only when asked for, as weights on /predict/)
-    extra = {**({} if body.loop is None else {"loop": body.loop}), **nucleus_args(body.top_p, body.min_p)}
+    extra = {**({} if body.loop is None else {"loop": body.loop}), **nucleus_args(body.top_p, body.min_p),
+             **({} if body.logprobs is None else {"logprobs": body.logprobs})}
     try:
         return model.generate(body.context, body.max_new_tokens, temperature=body.temperature, top_k=body.top_k,
                               seed=body.seed, stop_token=body.stop_token, pad_token=body.pad_token, weights=body.weights,
                               **extra)
     except IndexError as e:  # a context id outside the vocabulary is a bad request
+        raise ValueError(str(e))
+
+
+SCORE_MAX_IDS = 1 << 20  # scored ids per POST /score/ request
+SCORE_EXAMPLES = {
+    "single": {"summary": "One sequence", "description": "A word of a character model (vocabulary 27, id 0 ends a word): "
+                                                         "the log-probability and the rank of each of its ids, and the "
+                                                         "word's perplexity.",
+               "value": {"model_id": "names", "sequences": [5, 13, 13, 1, 0]}},
+    "batch": {"summary": "Held-out text, scalars only", "description": "Rows of different lengths in one request; only the "
+                                                                       "id count, mean negative log-probability, perplexity "
+                                                                       "and top-1 share come back.",
+              "value": {"model_id": "names", "sequences": [[5, 13, 13, 1, 0], [1, 22, 1, 0]], "details": False}},
+}
+
+
+@app.post("/score/")
+def score_sequences(body: ScoreRequest = Body(..., openapi_examples=SCORE_EXAMPLES)):
+    model_id = body.model_id
+    log.info(f"Requesting scores for model {model_id}")
+    rows = body.sequences if body.sequences and isinstance(body.sequences[0], list) else [body.sequences]
+    if sum(len(row) for row in rows if isinstance(row, list)) > SCORE_MAX_IDS:
+        raise ValueError(f"a request scores at most {SCORE_MAX_IDS} ids")
+    model = _cached_model(model_id)
+    try:
+        return model.score(body.sequences, pad_token=body.pad_token, weights=body.weights, details=body.details)
+    except IndexError as e:  # an id that is no class of the model is a bad request
         raise ValueError(str(e))
 
 

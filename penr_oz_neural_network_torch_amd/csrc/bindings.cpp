@@ -761,6 +761,43 @@ void sample_rows_op(const Tensor& logits, const Tensor& seq, const Tensor& done,
   PZ_HIP_CHECK(pz::sample_rows(a, cur_stream(logits)));
 }
 
+// the log-probability and the rank of targets[r] under row r of the logits (csrc/token_logprob.hip)
+void token_logprob_op(const Tensor& logits, const Tensor& targets, const Tensor& logprob, const optional<Tensor>& rank) {
+  const char* who = "pz::token_logprob: ";
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kFloat && logits.dim() == 2, who,
+              "logits must be a GPU fp32 [rows, V] tensor");
+  TORCH_CHECK(targets.is_cuda() && targets.scalar_type() == at::kLong && targets.dim() == 1, who,
+              "targets must be a GPU int64 [rows] tensor");
+  TORCH_CHECK(logprob.is_cuda() && logprob.scalar_type() == at::kFloat && logprob.dim() == 1, who,
+              "logprob must be a GPU fp32 [rows] tensor");
+  const bool has_rank = rank.has_value() && rank->defined();
+  if (has_rank)
+    TORCH_CHECK(rank->is_cuda() && rank->scalar_type() == at::kInt && rank->dim() == 1, who,
+                "rank must be a GPU int32 [rows] tensor");
+  const int64_t rows = logits.size(0), cols = logits.size(1);
+  TORCH_CHECK(targets.size(0) == rows && logprob.size(0) == rows && (!has_rank || rank->size(0) == rows), who,
+              "logits, targets, logprob and rank must have the same rows (", rows, ")");
+  TORCH_CHECK(targets.device() == logits.device() && logprob.device() == logits.device() &&
+                  (!has_rank || rank->device() == logits.device()),
+              who, "every tensor must be on the logits' device");
+  TORCH_CHECK(cols >= 1 && cols <= pz::kSampleMaxCols && rows <= INT32_MAX, who, "shape out of range: [", rows, ", ", cols, "]");
+  TORCH_CHECK(cols == 1 || logits.stride(1) == 1, who, "logits must have a unit column stride, got ", logits.stride(1));
+  TORCH_CHECK(rows <= 1 || logits.stride(0) >= cols, who, "logits rows overlap: row stride ", logits.stride(0), " < V = ", cols);
+  if (rows == 0) return;
+  pz::TokenLogprobArgs a{};
+  a.logits = logits.data_ptr<float>();
+  a.ld = logits.stride(0);
+  a.rows = rows;
+  a.cols = static_cast<int>(cols);
+  a.targets = targets.data_ptr<int64_t>();
+  a.targets_stride = targets.stride(0);
+  a.logprob = logprob.data_ptr<float>();
+  a.logprob_stride = logprob.stride(0);
+  a.rank = has_rank ? rank->data_ptr<int>() : nullptr;
+  a.rank_stride = has_rank ? rank->stride(0) : 0;
+  PZ_HIP_CHECK(pz::token_logprob(a, cur_stream(logits)));
+}
+
 // a whole generation request in one launch (csrc/generate_resident.hip). `plan` is the int list of
 // engine/resident.py: resident_plan. Whatever a wrong plan could turn into a stray LDS or global
 // access is refused here: the kernel trusts every number it is handed.
@@ -1445,6 +1482,7 @@ TORCH_LIBRARY(pz, m) {
   m.def("generate_resident(Tensor(a!) seq, Tensor(b!) done, Tensor[] params, int[] plan, int steps, float temperature, "
         "int top_k, int seed_lo, int seed_hi, int stop_token=-1, int row0=0, Tensor(c!)? logits_out=None, float top_p=1.0, "
         "float min_p=0.0) -> ()");
+  m.def("token_logprob(Tensor logits, Tensor targets, Tensor(a!) logprob, Tensor(b!)? rank) -> ()");
   m.def("softmax_bwd(Tensor g, Tensor y, Tensor(a!) dx) -> ()");
   m.def("colsum(Tensor x, Tensor(a!) out) -> ()");
   m.def("gather_rows(Tensor data, Tensor? indices, int seed_lo, int seed_hi, Tensor(a!) out, int rows_valid, "
@@ -1504,6 +1542,7 @@ TORCH_LIBRARY_IMPL(pz, CUDA, m) {
   m.impl("softmax_rows", TORCH_FN(softmax_rows_op));
   m.impl("sample_rows", TORCH_FN(sample_rows_op));
   m.impl("generate_resident", TORCH_FN(generate_resident_op));
+  m.impl("token_logprob", TORCH_FN(token_logprob_op));
   m.impl("softmax_bwd", TORCH_FN(softmax_bwd_op));
   m.impl("colsum", TORCH_FN(colsum_op));
   m.impl("gather_rows", TORCH_FN(gather_rows_op));

@@ -126,6 +126,23 @@ hipError_t sample_rows(const SampleArgs& a, hipStream_t s);
 constexpr int kSampleNarrowCols = 8192;     // up to here a row is sampled by 256 threads (sample_core.h)
 constexpr int kSampleScratchBytes = 16912;  // sizeof(SampleScratch): the sampler's LDS per workgroup
 
+// per row of fp32 logits, the log-probability (log-softmax) and the rank of one given column
+// (token_logprob.hip): sequence scoring. Strides in elements; rank may be null.
+constexpr int kTokenLogprobWaveCols = 1024;  // up to here a wave owns a row, beyond a workgroup does
+struct TokenLogprobArgs {
+  const float* logits;     // [rows][ld], ld >= cols, unit column stride
+  int64_t ld;
+  int64_t rows;
+  int cols;
+  const int64_t* targets;  // [rows]; outside [0, cols): logprob = NaN, rank = -1, nothing read through it
+  int64_t targets_stride;
+  float* logprob;          // [rows]: (l_t - max) - log(sum_c exp(l_c - max))
+  int64_t logprob_stride;
+  int* rank;               // [rows]: #{c : l_c > l_t} + #{c < t : l_c == l_t}
+  int64_t rank_stride;
+};
+hipError_t token_logprob(const TokenLogprobArgs& a, hipStream_t s);
+
 // one-launch token generation with the whole model in LDS (generate_resident.hip). The plan is
 // engine/resident.py's int list: kResHead header ints, kResParam per parameter, kResStage per stage.
 constexpr int kResMaxStages = 16, kResMaxParams = 64, kResMaxSteps = 4096;

@@ -67,6 +67,14 @@ copies, which are the e4m3 path's function exactly), the batchnorm running stati
 per call. The tokens are those ``PF.sample_rows`` draws from the kernel's own logits, which differ
 from the per-token loop's by fp32 summation order only. It is opt-in: a model that does not fit
 raises ``ValueError`` with the planner's reason, never a fall-back to the loop.
+
+Sequence scoring, :meth:`FusedPredictor.score` (the models that can generate): how likely the model
+finds ids it is given. ``seq [R, W]`` is uploaded and range-checked once; every window
+``seq[r, j : j + L]`` becomes a row of one ``[R * (W - L), L]`` matrix (torch views), which runs through
+``_logits`` in chunks of rows whose fp32 logits stay within ``SCORE_LOGITS_BYTES``; one
+``PF.token_logprob`` launch per chunk (csrc/token_logprob.hip) writes the log-probability and the rank
+of ``seq[r, L + j]`` straight into the ``[R, W - L]`` results, which stay on the device. It is also what
+``generate(..., logprobs=True)`` runs once, after its loop, on ``[context | tokens]``.
 """
 from __future__ import annotations
 
@@ -79,6 +87,7 @@ from .resident import RESIDENT_LDS_BYTES, describe_stages, resident_plan
 from .trainer import UnsupportedModel, compile_stages
 
 SKINNY_BELOW = 64  # rows from which the tiled GEMMs (M >= 64 on the matrix cores) take over
+SCORE_LOGITS_BYTES = 64 << 20  # score(): the fp32 logits of one chunk of windows stay within this
 
 
 class FusedPredictor:
@@ -308,6 +317,57 @@ class FusedPredictor:
         return seq[:, length:]
 
     # ------------------------------------------------------------------------------------
+    # sequence scoring (csrc/token_logprob.hip)
+    # ------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def score(self, seq: Tensor, weights: str | None = None, chunk_rows: int | None = None) -> tuple[Tensor, Tensor]:
+        """``seq``: int ids ``[R, W]`` with ``W > L`` = :attr:`context_length`. Returns ``(logprob fp32
+        [R, W - L], rank int32 [R, W - L])`` on the device: entry ``[r, j]`` is the log-probability and the
+        rank (0 = the most likely class) of ``seq[r, L + j]`` under the distribution the model gives the
+        window ``seq[r, j : j + L]`` (:func:`..ops.functional.token_logprob_reference`).
+
+        One upload, one range check (window ids as ``PF.embedding`` takes them, scored ids in
+        ``[0, classes)``), then per chunk of ``chunk_rows`` windows (default: as many as keep a chunk's
+        fp32 logits within ``SCORE_LOGITS_BYTES``) the forward kernels and one ``PF.token_logprob`` launch
+        that writes its slice of the results; nothing is read back inside the loop."""
+        fp8 = self._want_fp8(weights)
+        reason = self.generation_unsupported()
+        if reason is not None:
+            raise ValueError(reason)
+        length = self.context_length
+        seq = torch.as_tensor(seq)
+        if seq.dim() != 2 or seq.shape[1] <= length or seq.is_floating_point() or seq.dtype == torch.bool:
+            raise ValueError(f"seq must be an int tensor [rows, more than {length}], got {tuple(seq.shape)} {seq.dtype}")
+        width = self.stages[-1].out_width
+        if chunk_rows is None:
+            chunk_rows = max(1, SCORE_LOGITS_BYTES // (4 * width))
+        if isinstance(chunk_rows, bool) or not isinstance(chunk_rows, int) or chunk_rows < 1:
+            raise ValueError(f"chunk_rows must be an integer >= 1, got {chunk_rows!r}")
+        seq = seq.to(device=self.dev, dtype=torch.int64)
+        rows, scored = seq.shape[0], seq.shape[1] - length
+        logprob = torch.empty(rows, scored, device=self.dev, dtype=torch.float32)
+        rank = torch.empty(rows, scored, device=self.dev, dtype=torch.int32)
+        if rows == 0:
+            return logprob, rank
+        vocab = self.store.view(self.stages[0].seg_w).shape[0]
+        # once, one read (the loop skips the id check): PF.check_index_range's rule for the context columns as
+        # PF.embedding takes them, and for the scored columns as classes (width <= vocab: they are valid inputs too)
+        lo_c, hi_c, lo_t, hi_t = torch.stack(torch.aminmax(seq[:, :length]) + torch.aminmax(seq[:, length:])).tolist()
+        if lo_c < -vocab or hi_c >= vocab:
+            raise IndexError(f"index {lo_c if lo_c < -vocab else hi_c} is out of bounds for size {vocab}")
+        if lo_t < 0 or hi_t >= width:
+            raise IndexError(f"Target {lo_t if lo_t < 0 else hi_t} is out of bounds for size {width}")
+        # window i = r * scored + j holds seq[r, j : j + L] and is scored on seq[r, L + j]
+        windows = seq.unfold(1, length, 1)[:, :scored].reshape(rows * scored, length)
+        targets = seq[:, length:].reshape(-1)
+        lp, rk = logprob.view(-1), rank.view(-1)
+        for i0 in range(0, rows * scored, chunk_rows):
+            i1 = min(i0 + chunk_rows, rows * scored)
+            logits = self._logits(windows[i0:i1], fp8, check_ids=False).reshape(i1 - i0, width)
+            PF.token_logprob(logits, targets[i0:i1], lp[i0:i1], rk[i0:i1])
+        return logprob, rank
+
+    # ------------------------------------------------------------------------------------
     # one-launch generation (csrc/generate_resident.hip)
     # ------------------------------------------------------------------------------------
     def resident_plan(self, budget: int = RESIDENT_LDS_BYTES):
@@ -371,4 +431,4 @@ class FusedPredictor:
         return seq[:, length:]
 
 
-__all__ = ["FusedPredictor", "UnsupportedModel", "SKINNY_BELOW", "resident_plan", "RESIDENT_LDS_BYTES"]
+__all__ = ["FusedPredictor", "UnsupportedModel", "SKINNY_BELOW", "SCORE_LOGITS_BYTES", "resident_plan", "RESIDENT_LDS_BYTES"]

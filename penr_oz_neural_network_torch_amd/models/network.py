@@ -21,6 +21,7 @@ replaced atomically; periodic checkpoints of long trainings are written by a bac
 from __future__ import annotations
 
 import logging
+import math
 import random
 import time
 from datetime import datetime
@@ -371,7 +372,7 @@ class NeuralNetworkModel(MultiLayerPerceptron):
     def generate(self, context: list, max_new_tokens: int, temperature: float = 1.0, top_k: int | None = None,
                  seed: int | None = None, stop_token: int | None = None, pad_token: int = 0,
                  weights: str | None = None, loop: str | None = None, top_p: float | None = None,
-                 min_p: float | None = None) -> dict:
+                 min_p: float | None = None, logprobs: bool = False) -> dict:
         """Sample ``max_new_tokens`` ids after ``context`` from a next-token model (embedding first,
         softmax head): ``{"tokens": [[...], ...], "seed": int}``, one row per context row.
 
@@ -397,8 +398,17 @@ class NeuralNetworkModel(MultiLayerPerceptron):
         copied into every row's workgroup LDS and the token loop runs inside one kernel. It needs a GPU
         model with a fused predictor whose parameters fit (160 KiB of LDS, at most 8192 classes);
         anything else raises ``ValueError`` with the reason — there is no silent fall-back to the
-        per-token loop. ``None`` is the per-token loop."""
+        per-token loop. ``None`` is the per-token loop.
+
+        ``logprobs=True`` adds ``"logprobs"``: for every returned token its log-probability under the
+        model's own distribution — temperature 1 and no truncation, whatever ``temperature``, ``top_k``,
+        ``top_p`` and ``min_p`` drew it with (a token that top-k sampling drew has the probability the
+        whole vocabulary leaves it). It is computed after the loop by one :meth:`score` pass over
+        ``[context | tokens]`` (one batched forward, with the loop's ``weights``), and cut after
+        ``stop_token`` as the tokens are. Unset, nothing is computed and the key is absent."""
         from ..ops import functional as PF
+        if not isinstance(logprobs, bool):
+            raise ValueError(f"logprobs must be a boolean, got {logprobs!r}")
         if loop is not None:
             if loop != "resident":
                 raise ValueError(f"unknown loop {loop!r}: None (one sampling launch per token) or 'resident'")
@@ -456,16 +466,27 @@ class NeuralNetworkModel(MultiLayerPerceptron):
             for layer in self.layers:
                 layer.training = False
             if loop is not None:
-                tokens = predictor.generate_resident(ids, max_new_tokens, temperature=float(temperature), top_k=top_k,
-                                                     seed=key, stop_token=stop_token, weights=weights, **extra).tolist()
+                drawn = predictor.generate_resident(ids, max_new_tokens, temperature=float(temperature), top_k=top_k,
+                                                    seed=key, stop_token=stop_token, weights=weights, **extra)
             elif predictor is not None:
-                tokens = predictor.generate(ids, max_new_tokens, temperature=float(temperature), top_k=top_k, seed=key,
-                                            stop_token=stop_token, weights=weights, **extra).tolist()
+                drawn = predictor.generate(ids, max_new_tokens, temperature=float(temperature), top_k=top_k, seed=key,
+                                           stop_token=stop_token, weights=weights, **extra)
             else:
-                tokens = self._generate_layers(ids, max_new_tokens, float(temperature), top_k, key, stop_token, **extra)
+                drawn = self._generate_layers(ids, max_new_tokens, float(temperature), top_k, key, stop_token, **extra)
+            tokens = drawn.tolist() if isinstance(drawn, Tensor) else drawn
+            scores = None
+            if logprobs:  # one batched forward on [context | tokens], after the loop
+                full = torch.cat([ids.to(self.device), torch.as_tensor(drawn).to(self.device)], dim=1)
+                if predictor is not None:
+                    scores = predictor.score(full, weights=weights)[0].tolist()
+                else:
+                    scores = self._score_layers(full)[0].tolist()
+        result = {"tokens": tokens, "seed": seed}
         if stop_token is not None:
-            tokens = [row[:row.index(stop_token) + 1] if stop_token in row else row for row in tokens]
-        return {"tokens": tokens, "seed": seed}
+            result["tokens"] = [row[:row.index(stop_token) + 1] if stop_token in row else row for row in tokens]
+        if scores is not None:
+            result["logprobs"] = [lp[:len(row)] for lp, row in zip(scores, result["tokens"])]
+        return result
 
     def _generate_layers(self, ids: Tensor, steps: int, temperature: float, top_k, key, stop_token, **nucleus) -> list:
         """The generation loop through the layers (``_forward`` in eval mode) with the pure-torch sampler."""
@@ -481,6 +502,99 @@ class NeuralNetworkModel(MultiLayerPerceptron):
                 done |= token == stop_token
             seq[:, length + s] = token
         return seq[:, length:].tolist()
+
+    # ------------------------------------------------------------------------------------
+    # sequence scoring
+    # ------------------------------------------------------------------------------------
+    SCORE_MAX_IDS = 1 << 24  # scored ids per call (the padded batch is one tensor on the device)
+    SCORE_LAYERS_BYTES = 64 << 20  # _score_layers: the fp64 log-softmax of one chunk of windows stays within this
+
+    def score(self, sequences: list, pad_token: int = 0, weights: str | None = None, details: bool = True) -> dict:
+        """How likely a next-token model (embedding first, softmax head) finds ``sequences``: one non-empty
+        id list or a non-empty batch of non-empty lists. Every id of a row is scored given the
+        :attr:`context_length` ids before it; a row is left-padded with ``pad_token``, the convention of
+        :meth:`generate` for short contexts, so its first id is scored after a window of padding. Rows of
+        different lengths are padded on the right and the padding is masked out.
+
+        Returns ``{"tokens": n, "nll": ..., "perplexity": ..., "top1": ...}``: the number of scored ids, their
+        mean negative log-probability (natural log; summed in fp64 where the model lives), its exponential,
+        and the share of ids that were the model's most likely class (rank 0, ties to the lowest index: what
+        greedy sampling picks). ``details=True`` adds ``"logprobs"`` and ``"ranks"``, one list per row, by the
+        rule of :func:`..ops.functional.token_logprob_reference`; without it only the four scalars leave the
+        device.
+
+        GPU models with a fused predictor run :meth:`..engine.predictor.FusedPredictor.score` (batched
+        forward kernels and one ``PF.token_logprob`` launch per chunk of windows). CPU models, the reference
+        runtime and models without a predictor run the layer loop in eval mode under ``no_grad`` with the
+        pure-torch rule. ``weights="fp8"`` as in :meth:`predict`. ``IndexError`` for an id that is not a
+        class of the model."""
+        from ..ops import functional as PF
+        if weights is not None:
+            if weights != "fp8":
+                raise ValueError(f"unknown weights {weights!r}: None (the model's own precision) or 'fp8'")
+            if not self.on_gpu:
+                raise ValueError("weights='fp8' needs a model on a GPU (the e4m3 kernels are HIP kernels)")
+        if not isinstance(details, bool):
+            raise ValueError(f"details must be a boolean, got {details!r}")
+        vocab, classes = self._generation_shape()
+        if isinstance(pad_token, bool) or not isinstance(pad_token, int) or not 0 <= pad_token < vocab:
+            raise ValueError(f"pad_token {pad_token!r} is outside the vocabulary of {vocab}")
+        if not isinstance(sequences, list) or not sequences:
+            raise ValueError("sequences must be a non-empty id list or a non-empty batch of non-empty id lists")
+        batch = sequences if isinstance(sequences[0], list) else [sequences]
+        for row in batch:
+            if not isinstance(row, list) or not row or any(isinstance(v, bool) or not isinstance(v, int) for v in row):
+                raise ValueError("sequences rows must be non-empty lists of integer ids")
+        lengths = [len(row) for row in batch]
+        count, longest, length = sum(lengths), max(lengths), self.context_length
+        if len(batch) * longest > self.SCORE_MAX_IDS:
+            raise ValueError(f"too many ids to score in one call: {len(batch)} rows of up to {longest} "
+                             f"(at most {self.SCORE_MAX_IDS} with the padding)")
+        # [pad] * L, the row, then zeros (masked: any class would do) up to the longest row
+        ids = torch.tensor([[pad_token] * length + row + [0] * (longest - len(row)) for row in batch], dtype=torch.int64)
+        valid = torch.arange(longest).unsqueeze(0) < torch.tensor(lengths).unsqueeze(1)
+        PF.check_index_range(ids[:, length:].reshape(-1), 0, classes, "Target")  # IndexError, as generate
+        with torch.no_grad():
+            predictor = self._fused_predictor() if self.on_gpu else None
+            if weights is not None and predictor is None:
+                raise ValueError(f"weights='fp8' is not available for model {self.model_id}: "
+                                 f"{getattr(self, '_predictor_reason', 'no fused predictor')}")
+            for layer in self.layers:
+                layer.training = False
+            if predictor is not None:
+                logprob, rank = predictor.score(ids, weights=weights)
+            else:
+                logprob, rank = self._score_layers(ids)
+            valid = valid.to(logprob.device)
+            total = torch.where(valid, logprob.double(), torch.zeros((), dtype=torch.float64, device=logprob.device)).sum()
+            first = ((rank == 0) & valid).sum().double()
+            total, first = torch.stack([total, first]).tolist()  # the one download without details
+            nll = -total / count
+            result = {"tokens": count, "nll": nll, "perplexity": math.inf if nll >= 709 else math.exp(nll),  # (no OverflowError)
+                      "top1": first / count}
+            if details:
+                result["logprobs"] = [row[:n] for row, n in zip(logprob.tolist(), lengths)]
+                result["ranks"] = [row[:n] for row, n in zip(rank.tolist(), lengths)]
+        return result
+
+    def _score_layers(self, ids: Tensor) -> tuple[Tensor, Tensor]:
+        """The scorer through the layers (``_forward`` in eval mode) with the pure-torch rule: ``ids [R, L + n]``
+        -> ``(fp64 logprob [R, n], int64 rank [R, n])`` of the columns from ``L`` on, in chunks of windows."""
+        from ..ops import functional as PF
+        rows, length = ids.shape[0], self.context_length
+        scored = ids.shape[1] - length
+        ids = ids.to(self.device)
+        windows = ids.unfold(1, length, 1)[:, :scored].reshape(rows * scored, length)
+        targets = ids[:, length:].reshape(-1)
+        classes = self._generation_shape()[1]
+        chunk = max(1, self.SCORE_LAYERS_BYTES // (8 * classes))
+        logprob, rank = [], []
+        for i0 in range(0, rows * scored, chunk):
+            logits = self._forward(windows[i0:i0 + chunk], None)[0][-2].detach()  # the softmax layer's input
+            lp, rk = PF.token_logprob_reference(logits.reshape(-1, classes), targets[i0:i0 + chunk])
+            logprob.append(lp)
+            rank.append(rk)
+        return torch.cat(logprob).view(rows, scored), torch.cat(rank).view(rows, scored)
 
     def _forward(self, input_tensor: Tensor, target: list, dropout_rate=0.0) -> Tuple[list[Tensor], Tensor]:
         target_specified = target is not None and (isinstance(target, Tensor) or all(t is not None for t in target))

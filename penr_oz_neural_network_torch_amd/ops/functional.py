@@ -541,6 +541,53 @@ def generate_resident(seq: Tensor, done: Tensor, params: list[Tensor], plan: lis
                              **nucleus_args(top_p, min_p))
 
 
+# --------------------------------------------------------------------------------------------
+# sequence scoring (csrc/token_logprob.hip)
+# --------------------------------------------------------------------------------------------
+def token_logprob_reference(logits: Tensor, targets: Tensor) -> tuple[Tensor, Tensor]:
+    """The rule of :func:`token_logprob` in pure torch, on CPU or GPU tensors: ``logits [rows, V]`` (or
+    ``[V]``) of any float dtype and int ``targets [rows]`` -> ``(fp64 logprob [rows], int64 rank [rows])``.
+    It is the scorer of the runtimes without the kernel and the yardstick of the kernel's tests.
+
+    * ``logprob = log_softmax(logits.double())[target]``: a ``-inf`` target gives ``-inf``, ``-inf``
+      columns contribute nothing;
+    * ``rank = #{c : l_c > l_t} + #{c < t : l_c == l_t}``, compared in the logits' own dtype
+      (``-0 == +0``): rank 0 is the column greedy sampling picks, the lowest index among the maxima;
+    * a target outside ``[0, V)`` gives ``NaN`` / ``-1``."""
+    lg = logits.detach()
+    lg = lg.unsqueeze(0) if lg.dim() == 1 else lg.reshape(-1, lg.shape[-1])
+    rows, v = lg.shape
+    t = torch.as_tensor(targets).detach().reshape(-1).to(device=lg.device, dtype=torch.int64)
+    if t.shape[0] != rows:
+        raise ValueError(f"targets must hold one id per row of the logits: {t.shape[0]} ids, {rows} rows")
+    if v < 1:
+        raise ValueError("logits must have at least one column")
+    valid = (t >= 0) & (t < v)
+    tc = t.clamp(0, v - 1).unsqueeze(1)
+    logprob = torch.log_softmax(lg.double(), dim=-1).gather(1, tc).squeeze(1)
+    lt = lg.gather(1, tc)
+    before = torch.arange(v, device=lg.device).unsqueeze(0) < tc
+    rank = ((lg > lt) | ((lg == lt) & before)).sum(dim=-1)
+    return (torch.where(valid, logprob, torch.full_like(logprob, math.nan)),
+            torch.where(valid, rank, torch.full_like(rank, -1)))
+
+
+def token_logprob(logits: Tensor, targets: Tensor, logprob: Tensor | None = None,
+                  rank: Tensor | None = None) -> tuple[Tensor, Tensor | None]:
+    """Per row of the fp32 ``logits [rows, V]`` (unit column stride, any row stride ``>= V``), the
+    log-probability of ``targets[row]`` (int64 ``[rows]``, any stride) into ``logprob`` (fp32 ``[rows]``,
+    any stride; allocated when ``None``) and, when ``rank`` (int32 ``[rows]``, any stride) is given, its
+    rank by the rule of :func:`token_logprob_reference` (csrc/token_logprob.hip; one launch, nothing
+    comes back to the host). Returns ``(logprob, rank)``; ``rank=None`` computes no rank and returns
+    ``None`` for it. The call is bit-reproducible and a row's result does not depend on the rows sent
+    with it. The binding refuses tensors of another dtype, device or length and a non-unit column
+    stride; no rows is no launch."""
+    if logprob is None:
+        logprob = torch.empty(logits.shape[0], device=logits.device, dtype=torch.float32)
+    _ops().token_logprob(logits, targets, logprob, rank)
+    return logprob, rank
+
+
 def check_index_range(idx: Tensor, lo: int, hi: int, what: str, size: int | None = None) -> None:
     """Raise IndexError (as ATen / Python indexing do) unless every id is in ``[lo, hi)``.
     The HIP kernels never read outside their tables either way, but a bad id must surface as an
@@ -739,4 +786,4 @@ def tensor_summary(t: Tensor, algo: str | None, bins: int) -> dict:
 __all__ = ["gemm", "gemm_path", "gemm_last_kernel", "gemm_skinny", "gemm_skinny_eligible", "gemm_skinny_w8", "gemm_skinny_w8_eligible",
            "quantize_cols", "quantize_cols_reference", "dequantize_cols", "linear", "activation", "dropout", "softmax", "cross_entropy", "mse_loss",
            "batchnorm", "embedding", "tensor_summary", "epi_spec", "new_seed", "sample_rows", "sample_rows_reference", "nucleus_args",
-           "sample_uniform", "generate_resident"]
+           "sample_uniform", "generate_resident", "token_logprob", "token_logprob_reference"]
