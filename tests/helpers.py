@@ -1,4 +1,6 @@
 """Independent (numpy / plain torch) re-implementations used as references by the kernel tests."""
+import functools
+
 import numpy as np
 import torch
 
@@ -187,3 +189,62 @@ def histogram_reference(values, lo: float, hi: float, bins: int) -> np.ndarray:
     k = k[(k >= lo8) & (k <= hi8)]
     b = np.minimum(((k - lo8) * bins) // (hi8 - lo8), bins - 1)
     return np.bincount(b, minlength=bins).astype(np.int64)
+
+
+# ------------------------------------------------------------------------------------ exact GEMM
+def exact_operands(M: int, N: int, K: int, a_kc: bool, b_kc: bool, seed: int):
+    """bf16 ``a`` ([M, K] if ``a_kc`` else [K, M]) and ``b`` ([N, K] if ``b_kc`` else [K, N]) with
+    integer entries in [-4, 4] from a CPU generator, and the fp64 ``z = op(a) @ op(b)``. Every
+    partial sum of ``z`` is an integer below 16 K < 2^24, so every fp32 accumulation order gives ``z``."""
+    assert K * 16 < 2 ** 24
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    a = torch.randint(-4, 5, (M, K) if a_kc else (K, M), generator=g).to(torch.bfloat16)
+    b = torch.randint(-4, 5, (N, K) if b_kc else (K, N), generator=g).to(torch.bfloat16)
+    return a, b, (a.double() if a_kc else a.double().t()) @ (b.double().t() if b_kc else b.double())
+
+
+def gemm_epilogue_reference(z: torch.Tensor, *, alpha: float, bias, mode: int, act: int, keep_pre, keep_post,
+                            scale: float, aux=None, bits=None, c_old=None):
+    """fp64 value the GEMM epilogue stores for the fp64 product ``z``, and its column sums (the
+    ``colsum`` side output sums the values before they are rounded to the output type).
+    ``mode`` 0 (EPI_STORE): ``alpha z + bias``; 1 (EPI_FWD): ``drop_post(act(drop_pre(alpha z + bias)))``;
+    2 (EPI_BWD): ``alpha z`` through the stage's derivative, from the stored output ``aux`` or, for a
+    ReLU stage, from ``bits`` = (y > 0): ``g * bits * scale_pre * scale_post`` (a keep mask that is
+    not None switches that dropout's scale on; its entries are already part of ``bits``).
+    ``c_old``: the previous C of an accumulating GEMM, added last."""
+    h = z.double() * alpha
+    if mode == 2:
+        assert bias is None
+        if bits is not None:
+            total = (scale if keep_pre is not None else 1.0) * (scale if keep_post is not None else 1.0)
+            out = h * bits.double() * total
+        else:
+            out = stage_bwd_reference(h, aux, act, keep_pre, keep_post, scale)
+    else:
+        if bias is not None:
+            h = h + bias.double()
+        out = h if mode == 0 else stage_fwd_reference(h, act, keep_pre, keep_post, torch.tensor(scale, dtype=torch.float64))
+    if c_old is not None:
+        out = out + c_old.double()
+    return out, out.sum(0)
+
+
+def assert_gemm_exact(out: torch.Tensor, ref64: torch.Tensor) -> None:
+    """``out`` holds exactly the fp64 reference rounded once to its dtype. The reference must be
+    fp32-representable (the kernels' epilogue math is fp32: only then is "exact" meaningful); the
+    comparison is by value, so -0 equals +0."""
+    assert torch.isfinite(out).all()
+    assert torch.equal(ref64.float().double(), ref64), "the reference is not exact in fp32"
+    want = ref64.float().to(out.dtype)
+    if not torch.equal(out.float(), want.float()):
+        bad = out.float() != want.float()
+        i = bad.nonzero()[0].tolist()
+        raise AssertionError(f"{int(bad.sum())} of {bad.numel()} elements differ; first at {i}: "
+                             f"{out[tuple(i)].item()} != {want[tuple(i)].item()}")
+
+
+@functools.lru_cache(maxsize=64)
+def keep2d_cached(rows: int, cols: int, idx_ld: int, seed: tuple[int, int], lid: int, p: float) -> torch.Tensor:
+    """:func:`keep2d`, remembered per argument tuple (15.7 M elements take about a second in numpy);
+    callers must not modify the result."""
+    return keep2d(rows, cols, idx_ld, seed, lid, p)

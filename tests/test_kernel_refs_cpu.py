@@ -5,8 +5,9 @@ import pytest
 import torch
 
 from penr_oz_neural_network_torch_amd.ops import functional as PF
-from tests.helpers import (fp8_code_values, fp8_encode_reference, fp8_tie_points, gather_picks, gather_seed,
-                           histogram_reference, keep2d, keep_mask)
+from tests.helpers import (ACT_FWD, assert_gemm_exact, exact_operands, fp8_code_values, fp8_encode_reference,
+                           fp8_tie_points, gather_picks, gather_seed, gemm_epilogue_reference, histogram_reference,
+                           keep2d, keep2d_cached, keep_mask, stage_bwd_reference, stage_fwd_reference)
 
 M32 = 0xFFFFFFFF
 
@@ -102,3 +103,107 @@ def test_degenerate_histogram_bin(bins):
     want = [0] * bins
     want[bins // 2] = 10
     assert h.tolist() == want
+
+
+# ------------------------------------------------------------------------------------ exact GEMM
+@pytest.mark.parametrize("a_kc,b_kc", [(True, True), (True, False), (False, True), (False, False)])
+def test_exact_operands_match_python_int_dot_products(a_kc, b_kc):
+    M, N, K = 37, 29, 96
+    a, b, z = exact_operands(M, N, K, a_kc, b_kc, seed=5)
+    assert a.dtype == b.dtype == torch.bfloat16 and z.dtype == torch.float64 and z.shape == (M, N)
+    assert a.shape == ((M, K) if a_kc else (K, M)) and b.shape == ((N, K) if b_kc else (K, N))
+    for t in (a, b):
+        assert torch.equal(t.double(), t.double().round()) and t.min() == -4 and t.max() == 4
+    al, bl = a.int().tolist(), b.int().tolist()
+    for m, n in [(0, 0), (M - 1, N - 1), (3, 17), (36, 0), (11, 28)]:
+        dot = sum((al[m][k] if a_kc else al[k][m]) * (bl[n][k] if b_kc else bl[k][n]) for k in range(K))
+        assert z[m, n].item() == dot
+    a2, _, z2 = exact_operands(M, N, K, a_kc, b_kc, seed=5)
+    assert torch.equal(a, a2) and torch.equal(z, z2)
+    assert not torch.equal(a, exact_operands(M, N, K, a_kc, b_kc, seed=6)[0])
+    with pytest.raises(AssertionError):
+        exact_operands(8, 8, 2 ** 20, a_kc, b_kc, seed=1)
+
+
+def test_assert_gemm_exact_demands_an_fp32_exact_reference_and_equal_values():
+    _, _, z = exact_operands(16, 24, 64, True, False, seed=2)
+    eighths = torch.arange(-12, 12, dtype=torch.float64) / 8
+    ref, _ = gemm_epilogue_reference(z, alpha=0.5, bias=eighths, mode=0, act=0, keep_pre=None, keep_post=None, scale=1.0)
+    assert_gemm_exact(ref.to(torch.bfloat16), ref)
+    assert_gemm_exact(ref.float(), ref)
+    relu = ref.clamp_min(0.0)
+    assert (relu == 0).any()
+    assert_gemm_exact(torch.where(relu == 0, torch.tensor(-0.0), relu.float()), relu)  # -0 equals the reference's +0
+    third, _ = gemm_epilogue_reference(z, alpha=0.5, bias=torch.full((24,), 1 / 3, dtype=torch.float64), mode=0, act=0,
+                                       keep_pre=None, keep_post=None, scale=1.0)
+    with pytest.raises(AssertionError, match="not exact in fp32"):
+        assert_gemm_exact(third.float(), third)
+    off = ref.float().clone()
+    off[3, 5] = torch.nextafter(off[3, 5], torch.tensor(float("inf")))
+    with pytest.raises(AssertionError, match="1 of 384 elements differ"):
+        assert_gemm_exact(off, ref)
+    nan = ref.float().clone()
+    nan[0, 0] = float("nan")
+    with pytest.raises(AssertionError):
+        assert_gemm_exact(nan, ref)
+
+
+@pytest.mark.parametrize("act", [0, 1, 2, 3])
+@pytest.mark.parametrize("pre,post", [(False, False), (True, False), (False, True), (True, True)])
+def test_gemm_epilogue_reference_forward_is_the_stage_reference(act, pre, post):
+    M, N, p = 24, 40, 0.5
+    _, _, z = exact_operands(M, N, 64, True, False, seed=3)
+    bias = torch.arange(N, dtype=torch.float64) / 8 - 2
+    kp = keep2d(M, N, N + 8, (1, 2), 3, p) if pre else None
+    kq = keep2d(M, N, N + 8, (1, 2), 4, p) if post else None
+    got, cs = gemm_epilogue_reference(z, alpha=0.25, bias=bias, mode=1, act=act, keep_pre=kp, keep_post=kq, scale=2.0)
+    h = z * 0.25 + bias
+    want = stage_fwd_reference(h, act, kp, kq, torch.tensor(2.0, dtype=torch.float64))
+    assert got.dtype == torch.float64 and torch.equal(got, want) and torch.equal(cs, want.sum(0))
+    # by hand, element by element
+    m1 = kp.double() * 2 if pre else 1.0
+    m2 = kq.double() * 2 if post else 1.0
+    assert torch.equal(got, ACT_FWD[act](h * m1) * m2)
+    store, _ = gemm_epilogue_reference(z, alpha=0.25, bias=bias, mode=0, act=act, keep_pre=kp, keep_post=kq, scale=2.0)
+    assert torch.equal(store, h)
+    acc, _ = gemm_epilogue_reference(z, alpha=0.25, bias=None, mode=0, act=0, keep_pre=None, keep_post=None, scale=1.0,
+                                     c_old=torch.ones(M, N))
+    assert torch.equal(acc, z * 0.25 + 1)
+
+
+@pytest.mark.parametrize("pre,post", [(False, False), (True, False), (False, True), (True, True)])
+def test_gemm_epilogue_reference_bitmask_backward_is_the_stage_backward(pre, post):
+    """A ReLU stage's stored y is positive exactly where z > 0 and both dropouts kept: the bitmask
+    form (bits = y > 0, no keep masks consulted) equals the derivative chain from y."""
+    M, N, p, scale = 24, 40, 0.5, 2.0
+    _, _, g = exact_operands(M, N, 64, True, True, seed=4)
+    _, _, h = exact_operands(M, N, 32, True, False, seed=5)
+    kp = keep2d(M, N, N, (1, 2), 3, p) if pre else None
+    kq = keep2d(M, N, N, (1, 2), 4, p) if post else None
+    y = stage_fwd_reference(h, 1, kp, kq, torch.tensor(scale, dtype=torch.float64))
+    bits = y > 0
+    assert 0.05 < bits.double().mean() < 0.6
+    got, cs = gemm_epilogue_reference(g, alpha=0.5, bias=None, mode=2, act=1, keep_pre=kp, keep_post=kq, scale=scale,
+                                      bits=bits)
+    want = stage_bwd_reference(g * 0.5, y, 1, kp, kq, scale)
+    assert torch.equal(got, want) and torch.equal(cs, want.sum(0))
+    from_aux, _ = gemm_epilogue_reference(g, alpha=0.5, bias=None, mode=2, act=1, keep_pre=kp, keep_post=kq, scale=scale,
+                                          aux=y)
+    assert torch.equal(from_aux, want)
+    assert torch.equal(got, g * 0.5 * bits * (2.0 if pre else 1.0) * (2.0 if post else 1.0))
+
+
+def test_keep2d_cached_is_keep2d():
+    a = keep2d_cached(5, 10, 16, (3, 4), 2, 0.25)
+    assert torch.equal(a, keep2d(5, 10, 16, (3, 4), 2, 0.25)) and keep2d_cached(5, 10, 16, (3, 4), 2, 0.25) is a
+
+
+def test_half_dropout_is_exact_in_the_kernels_arithmetic():
+    """p = 0.5: the scale, its square and its inverse are powers of two, the threshold is the top bit."""
+    ei, ef = PF.epi_spec(PF.ACT_RELU, 3, 4, 0.5, (1, 2))
+    assert ei[5] == 32768 and ei[6] == 0 and ef == [2.0, 0.5]
+    ei, ef = PF.epi_spec(PF.ACT_RELU, 3, 4, 0.3, (1, 2))
+    assert ei[5] == 19661
+    ei, ef = PF.epi_spec(PF.ACT_RELU, 3, 4, 1.0, (1, 2))
+    assert ei[5] == 65536 and ei[6] == 1 and ef[0] == 0.0
+    assert not keep_mask(64, 1, 2, 3, 1.0).any()
