@@ -248,3 +248,68 @@ def keep2d_cached(rows: int, cols: int, idx_ld: int, seed: tuple[int, int], lid:
     """:func:`keep2d`, remembered per argument tuple (15.7 M elements take about a second in numpy);
     callers must not modify the result."""
     return keep2d(rows, cols, idx_ld, seed, lid, p)
+
+
+# ---------------------------------------------------------------------------- exact fp8 GEMM / split plans
+def exact_operands_fp8(M: int, N: int, K: int, a_kc: bool, b_kc: bool, fmt_a, fmt_b, seed: int):
+    """:func:`exact_operands` cast to the fp8 formats ``fmt_a`` / ``fmt_b``: integers in [-4, 4] are
+    exact in e4m3 and in e5m2, so ``z`` is the fp64 product of the fp8 values themselves."""
+    a, b, z = exact_operands(M, N, K, a_kc, b_kc, seed)
+    return a.to(fmt_a), b.to(fmt_b), z
+
+
+def fp8_all_codes(fmt):
+    """Every finite code of ``fmt`` (both signs, zeros and subnormals included, no NaN / inf) as a
+    uint8 tensor, and the fp64 value of each, from :func:`fp8_code_values`."""
+    table = fp8_code_values(fmt)
+    code = np.arange(len(table), dtype=np.uint8)
+    return torch.from_numpy(np.concatenate([code, code | 0x80])), torch.from_numpy(np.concatenate([table, -table]))
+
+
+K_FILL = 240  # workgroups that fill the device (kFill in csrc/gemm_mfma.hip)
+
+
+def _split_for(tiles: int, nk: int, factors) -> int:
+    for sp in factors:
+        if tiles * sp >= K_FILL and nk % sp == 0 and nk // sp >= 16:
+            return sp
+    return 0
+
+
+def gemm_split_plan(M: int, N: int, K: int, *, fp8: bool = False, b_kc: bool = False) -> int:
+    """``pz::gemm_split`` restated for an MFMA-eligible GEMM outside the bf16 fixed-kind 256x128 rule:
+    fp8 GEMMs with a K-contiguous B never split; otherwise the first factor of 2, 4, 8 that fills the
+    device with 256 x 256 tiles and leaves each slice >= 16 K steps (32 deep for bf16, 64 for fp8)."""
+    if fp8 and b_kc:
+        return 1
+    tiles = -(-M // 256) * -(-N // 256)
+    if tiles >= K_FILL:
+        return 1
+    return _split_for(tiles, K // (64 if fp8 else 32), (2, 4, 8)) or 1
+
+
+def gemm_pair_split_plan(shape0, shape1, K: int) -> int:
+    """``pz::gemm_pair_split`` restated for an eligible pair (whole 256-tiles, K % 64 == 0): the first
+    factor of 1, 2, 4, 8 that fills the device with both problems' tiles at >= 16 64-deep K steps a
+    slice; failing that 8 wherever 8 slices of >= 16 steps exist, else 1."""
+    tiles = (shape0[0] // 256) * (shape0[1] // 256) + (shape1[0] // 256) * (shape1[1] // 256)
+    nk = K // 64
+    return _split_for(tiles, nk, (1, 2, 4, 8)) or (8 if nk % 8 == 0 and nk // 8 >= 16 else 1)
+
+
+# the SGD hyper-parameters of the exact gemm_update tests: all powers of two, so that with an integer
+# gradient and p0 in multiples of 1/8 every intermediate of p0 - lr (g scale + 2 l2 p0) is exact in fp32
+SGD_EXACT = dict(lr=2.0 ** -6, grad_scale=0.5, l2=2.0 ** -4)
+
+# Split-K factors the GPU tests claim for their shapes (asserted there through gemm_last_kernel /
+# gemm_pair_split, and on the CPU against the two restatements above)
+FP8_SPLIT_CASES = [  # (M, N, K, b_kc, split): fp8 operands
+    ((1536, 2560, 4096), False, 4), ((1528, 2560, 4096), False, 4), ((1536, 1280, 8192), False, 8),
+    ((512, 768, 320), False, 1), ((512, 256, 320), False, 1), ((4096, 3840, 64), False, 1),
+    ((1536, 2560, 4096), True, 1), ((8192, 1024, 8192), True, 1)]
+PAIR_SPLIT_CASES = [  # ((M0, N0), (M1, N1), K, split)
+    ((256, 256), (256, 512), 64, 1), ((1536, 2560), (2560, 1536), 2048, 2), ((1536, 1280), (1280, 1536), 4096, 4),
+    ((256, 512), (512, 256), 8192, 8), ((4096, 3840), (256, 256), 1024, 1)]
+UPDATE_SPLIT_CASES = [  # (M, N, K, split): bf16 operands, fp32 state
+    ((256, 256, 64), 1), ((200, 136, 96), 1), ((4088, 3832, 64), 1), ((512, 4096, 512), 1), ((1536, 1280, 4096), 8),
+    ((1528, 1280, 4096), 8)]

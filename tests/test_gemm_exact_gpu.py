@@ -31,9 +31,10 @@ Dispatch cells reached (kFill = 240):
   mfma/var6/256x256/ek0/split8      Ssplit with ragged M (1528, 1280, 4096)
   generic/var0/64x64/ek0/split1     (67, 45, 23) forced, bf16 and fp32 operands; bf16 out + accumulate at S128
   sk/var0/256x256/ek1|3|4|5|6|100    (1536, 1280, 512) on 37 CUs (30 data-parallel tiles) and 200 (two K halves)
-Not reached on purpose: the !buffer_ok fallbacks (VAR 0; need a 4 GiB operand), fp8 operands
-(test_gemm_fp8_*; whether the f8f6f4 MFMA sums small integers exactly is not measured), gemm_pair,
-gemm_update (EPI_OPT), fp32 outputs of the stream-K engine outside the dW layout (it has none).
+Not reached on purpose: the !buffer_ok fallbacks (VAR 0; need a 4 GiB operand), fp32 outputs of the
+stream-K engine outside the dW layout (it has none). fp8 operands run through this file's run_case
+from test_gemm_fp8_exact_gpu.py (its ``fmts`` / ``layout`` / ``q8`` arguments); gemm_pair and
+gemm_update (EPI_OPT) are in test_gemm_pair_update_gpu.py.
 
 Measured on MI355X (the file takes about 17 s): every kernel name above as predicted from
 launch_tiles, every none / ReLU form at p = 0.5 and 1.0 exact. Worst err / bound: p = 0.3 kept values
@@ -55,8 +56,8 @@ import pytest
 import torch
 
 from penr_oz_neural_network_torch_amd.ops import functional as PF
-from tests.helpers import (assert_gemm_exact, exact_operands, fp8_encode_reference, gemm_epilogue_reference,
-                           keep2d_cached)
+from tests.helpers import (assert_gemm_exact, exact_operands, exact_operands_fp8, fp8_encode_reference,
+                           gemm_epilogue_reference, keep2d_cached)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -189,8 +190,10 @@ def expected_kernel(cls: str, form: str, no_split: bool = False) -> str:
 
 # ------------------------------------------------------------------------------------ inputs
 @functools.lru_cache(maxsize=None)
-def operands(M, N, K, a_kc, b_kc):
-    a, b, z = exact_operands(M, N, K, a_kc, b_kc, seed=M + 3 * N + 7 * K + 2 * a_kc + b_kc)
+def operands(M, N, K, a_kc, b_kc, fmts=None):
+    """Integer operands on the device: bf16, or (``fmts`` = the two fp8 formats) fp8."""
+    seed = M + 3 * N + 7 * K + 2 * a_kc + b_kc
+    a, b, z = exact_operands(M, N, K, a_kc, b_kc, seed) if fmts is None else exact_operands_fp8(M, N, K, a_kc, b_kc, *fmts, seed)
     return a.to(DEV), b.to(DEV), z.to(DEV)
 
 
@@ -231,15 +234,15 @@ def old_c(M, N):
     return torch.randint(-64, 65, (M, N), generator=g).to(DEV, F32)
 
 
-def framed(rows, cols, dtype, strided, fill=7.0, src=None):
-    """A [rows, cols] tensor: contiguous, or (``strided``) the column slice [:, 8 : 8 + cols] of a
-    tensor 16 columns wider and 8 rows taller. Returns (view, base); everything is ``fill`` (then ``src``)."""
+def framed(rows, cols, dtype, strided, fill=7.0, src=None, pad=8):
+    """A [rows, cols] tensor: contiguous, or (``strided``) the column slice [:, pad : pad + cols] of a
+    tensor 2 pad columns wider and 8 rows taller. Returns (view, base); everything is ``fill`` (then ``src``)."""
     if not strided:
         base = torch.full((rows, cols), fill, device=DEV, dtype=F32).to(dtype)
         view = base
     else:
-        base = torch.full((rows + 8, cols + 16), fill, device=DEV, dtype=F32).to(dtype)
-        view = base[:rows, 8:8 + cols]
+        base = torch.full((rows + 8, cols + 2 * pad), fill, device=DEV, dtype=F32).to(dtype)
+        view = base[:rows, pad:pad + cols]
     if src is not None:
         view.copy_(src)
     return view, base
@@ -249,8 +252,9 @@ def frame_untouched(view, base, fill=7.0):
     """Every element of ``base`` outside ``view`` still holds ``fill``."""
     if view is base:
         return True
+    pad = view.storage_offset() - base.storage_offset()
     probe = base.float()
-    probe[:view.shape[0], 8:8 + view.shape[1]] = fill
+    probe[:view.shape[0], pad:pad + view.shape[1]] = fill
     return bool((probe == fill).all())
 
 
@@ -261,7 +265,7 @@ def alpha_of(f: Form, K: int) -> float:
         # h ~ N(0, 1): var(a b) = (60 / 9)^2 for integers uniform in [-4, 4], so std(z) = 6.67 sqrt(K)
         return 2.0 ** -round(0.5 * math.log2(44.4 * K))
     if f.out8 and f.mode == PF.EPI_FWD:
-        return 16.0 if K <= 128 else 2.0   # |y| 2^-3 passes 448 on some elements: the e4m3 clamp runs
+        return 16.0 if K <= 192 else 2.0   # |y| 2^-3 passes 448 on some elements: the e4m3 clamp runs
     return 0.5
 
 
@@ -282,16 +286,37 @@ def fp8_codes_equal(got, y, qs, fmt):
     assert same.all(), (int((~same).sum()), g[~same][:4].tolist(), want[~same][:4].tolist())
 
 
+# fp8 operands: the dequantisation scales (device scalars; powers of two). OUT8_Q: the out8 factors
+# "sat" (some outputs pass the format's largest value) and "sub" (some land on subnormal codes: the
+# smallest is 2^-9 / 2^-16, the smallest normal value 2^-6 / 2^-14)
+F8_SCALES = (0.25, 2.0 ** -6)
+OUT8_Q = {E4M3: dict(std=2.0 ** -3, sat=2.0 ** -3, sub=2.0 ** -8, tiny=2.0 ** -9, normal=2.0 ** -6, top=448.0),
+          E5M2: dict(std=2.0 ** -3, sat=2.0 ** 8, sub=2.0 ** -16, tiny=2.0 ** -16, normal=2.0 ** -14, top=57344.0)}
+
+
+@functools.lru_cache(maxsize=None)
+def dev_scalar(v):
+    return torch.tensor([v], device=DEV)
+
+
 def run_case(shape, form, p=0.5, *, engine=1, cus=0, force_generic=False, no_split=False, strided=False,
-             idx_ld=0, in_dtype=BF16, out_dtype=None, store_c=True):
-    """One GEMM launch of ``form`` checked against the fp64 reference. Returns what it produced."""
+             idx_ld=0, in_dtype=BF16, out_dtype=None, store_c=True, layout=None, fmts=None, q8="std"):
+    """One GEMM launch of ``form`` checked against the fp64 reference. Returns what it produced.
+    ``fmts`` = (format of A, format of B): fp8 operands in layout ``layout`` (default: the form's),
+    dequantised by F8_SCALES (folded into the reference's alpha; the kernel's alpha is raised by as
+    much, so that every form sees the values the bf16 run sees). ``q8``: which OUT8_Q factor the
+    fp8 copy takes ("std": 2^-3, at which e4m3 saturates too)."""
     M, N, K = shape
     f = FORMS[form]
-    a_kc, b_kc = LAYOUTS[f.layout]
-    a0, b0, z = operands(M, N, K, a_kc, b_kc)
+    a_kc, b_kc = LAYOUTS[layout or f.layout]
+    a0, b0, z = operands(M, N, K, a_kc, b_kc, fmts)
     out_dtype = out_dtype or f.out
     what = f"{form} {shape} p={p}"
     alpha = alpha_of(f, K)
+    k_alpha, scales = alpha, {}
+    if fmts is not None:
+        k_alpha = alpha / (F8_SCALES[0] * F8_SCALES[1])
+        scales = dict(scale_a=dev_scalar(F8_SCALES[0]), scale_b=dev_scalar(F8_SCALES[1]))
     scale = 0.0 if p >= 1.0 else 1.0 / (1.0 - p)
     ld = idx_ld or N
     kp = keep(M, N, ld, LID_PRE, p) if f.pre else None
@@ -299,8 +324,9 @@ def run_case(shape, form, p=0.5, *, engine=1, cus=0, force_generic=False, no_spl
     epi = PF.NO_EPI if f.mode == PF.EPI_STORE else PF.epi_spec(f.act, LID_PRE if f.pre else -1,
                                                                 LID_POST if f.post else -1, p, SEED)
     bias = bias_vec(N) if f.bias else None
-    a, _ = framed(*a0.shape, in_dtype, strided, src=a0)
-    b, _ = framed(*b0.shape, in_dtype, strided, src=b0)
+    # (fp8 operands: 16-byte aligned slices of rows that are a multiple of 16 bytes apart)
+    a, _ = framed(*a0.shape, in_dtype if fmts is None else fmts[0], strided, src=a0, pad=8 if fmts is None else 16)
+    b, _ = framed(*b0.shape, in_dtype if fmts is None else fmts[1], strided, src=b0, pad=8 if fmts is None else 16)
     aux = bits = mask = aux_v = aux_base = None
     if f.mode == PF.EPI_BWD:
         y_src, bits = stage_source(M, N, f.act, scale if f.post else 1.0)
@@ -318,13 +344,14 @@ def run_case(shape, form, p=0.5, *, engine=1, cus=0, force_generic=False, no_spl
     colsum = torch.zeros(N, device=DEV) if f.colsum else None
     fmt = E5M2 if f.mode == PF.EPI_BWD else E4M3
     o8 = o8_base = qs = amax = None
+    rule8, q8 = OUT8_Q[fmt], OUT8_Q[fmt][q8]
     if f.out8:
         o8, o8_base = framed(M, N, fmt, strided)
-        qs, amax = torch.tensor([2.0 ** -3], device=DEV), torch.zeros(1, device=DEV)
+        qs, amax = torch.tensor([q8], device=DEV), torch.zeros(1, device=DEV)
 
-    PF.gemm(a, a_kc, b, b_kc, c, bias=bias, aux=aux_v, colsum=colsum, mode=f.mode, epi=epi, alpha=alpha,
+    PF.gemm(a, a_kc, b, b_kc, c, bias=bias, aux=aux_v, colsum=colsum, mode=f.mode, epi=epi, alpha=k_alpha,
             accumulate=f.accumulate, idx_ld=idx_ld, force_generic=force_generic, mask=mask if not force_generic else None,
-            out8=o8, out8_qscale=qs, amax=amax, no_split=no_split, store_c=store_c, engine=engine, cus=cus)
+            out8=o8, out8_qscale=qs, amax=amax, no_split=no_split, store_c=store_c, engine=engine, cus=cus, **scales)
     name = PF.gemm_last_kernel()
     torch.cuda.synchronize()
 
@@ -370,10 +397,13 @@ def run_case(shape, form, p=0.5, *, engine=1, cus=0, force_generic=False, no_spl
             rows, mld = mask.shape
             assert (mask.reshape(rows // 256, mld // 32, 256, 32)[-1, :, M % 256:, :] == 0xAB).all(), what
     if o8 is not None:
-        if fmt == E4M3:
-            assert (y.double().abs() * 2.0 ** -3 > 448).any(), what
+        v8 = y.double().abs() * q8
+        if q8 == rule8["sub"]:
+            assert ((v8 >= rule8["tiny"]) & (v8 < rule8["normal"])).any(), what
+        if q8 == rule8["sat"]:
+            assert (v8 > rule8["top"]).any(), what
         if store_c:  # (store_c = False: the caller compares the codes with the storing run's)
-            fp8_codes_equal(o8, y, 2.0 ** -3, fmt)
+            fp8_codes_equal(o8, y, q8, fmt)
         assert amax.item() == y.float().abs().max().item(), what
         assert frame_untouched(o8, o8_base), what
     neg0 = int(((c == 0) & torch.signbit(c)).sum()) if store_c else 0

@@ -5,9 +5,11 @@ import pytest
 import torch
 
 from penr_oz_neural_network_torch_amd.ops import functional as PF
-from tests.helpers import (ACT_FWD, assert_gemm_exact, exact_operands, fp8_code_values, fp8_encode_reference,
-                           fp8_tie_points, gather_picks, gather_seed, gemm_epilogue_reference, histogram_reference,
-                           keep2d, keep2d_cached, keep_mask, stage_bwd_reference, stage_fwd_reference)
+from tests.helpers import (ACT_FWD, FP8_SPLIT_CASES, PAIR_SPLIT_CASES, SGD_EXACT, UPDATE_SPLIT_CASES, assert_gemm_exact,
+                           exact_operands, exact_operands_fp8, fp8_all_codes, fp8_code_values, fp8_encode_reference,
+                           fp8_tie_points, gather_picks, gather_seed, gemm_epilogue_reference, gemm_pair_split_plan,
+                           gemm_split_plan, histogram_reference, keep2d, keep2d_cached, keep_mask, opt_update_reference,
+                           stage_bwd_reference, stage_fwd_reference)
 
 M32 = 0xFFFFFFFF
 
@@ -207,3 +209,71 @@ def test_half_dropout_is_exact_in_the_kernels_arithmetic():
     ei, ef = PF.epi_spec(PF.ACT_RELU, 3, 4, 1.0, (1, 2))
     assert ei[5] == 65536 and ei[6] == 1 and ef[0] == 0.0
     assert not keep_mask(64, 1, 2, 3, 1.0).any()
+
+
+E4M3, E5M2 = torch.float8_e4m3fn, torch.float8_e5m2
+
+
+@pytest.mark.parametrize("fmt_a,fmt_b", [(E4M3, E4M3), (E5M2, E4M3), (E4M3, E5M2)])
+@pytest.mark.parametrize("a_kc,b_kc", [(True, True), (True, False), (False, False)])
+def test_exact_operands_fp8_round_trips_and_z_is_the_integer_product(fmt_a, fmt_b, a_kc, b_kc):
+    M, N, K = 24, 40, 64
+    a8, b8, z = exact_operands_fp8(M, N, K, a_kc, b_kc, fmt_a, fmt_b, seed=9)
+    a, b, z16 = exact_operands(M, N, K, a_kc, b_kc, seed=9)
+    assert a8.dtype == fmt_a and b8.dtype == fmt_b and a8.shape == a.shape and b8.shape == b.shape
+    # the cast changed nothing, and a second trip through the fp8 type changes nothing either
+    assert torch.equal(a8.double(), a.double()) and torch.equal(b8.double(), b.double())
+    assert torch.equal(a8.float().to(fmt_a).view(torch.uint8), a8.view(torch.uint8))
+    assert torch.equal(b8.float().to(fmt_b).view(torch.uint8), b8.view(torch.uint8))
+    ai, bi = a8.double().long(), b8.double().long()
+    assert ai.abs().max() == 4 and bi.abs().max() == 4
+    want = (ai if a_kc else ai.t()) @ (bi.t() if b_kc else bi)
+    assert z.dtype == torch.float64 and torch.equal(z, want.double()) and torch.equal(z, z16)
+
+
+@pytest.mark.parametrize("fmt", [E4M3, E5M2])
+def test_fp8_all_codes_is_the_code_table_and_fits_bf16(fmt):
+    codes, values = fp8_all_codes(fmt)
+    table = fp8_code_values(fmt)
+    n = len(table)
+    assert codes.dtype == torch.uint8 and len(codes) == 2 * n == len(set(codes.tolist()))
+    assert np.array_equal(values[:n].numpy(), table) and np.array_equal(values[n:].numpy(), -table)
+    assert torch.equal(codes[:n].long(), torch.arange(n)) and torch.equal(codes[n:].long(), torch.arange(n) + 128)
+    as_fp8 = codes.view(fmt)
+    assert torch.isfinite(as_fp8.float()).all() and torch.equal(as_fp8.double(), values)   # torch reads the codes alike
+    assert torch.equal(values.to(torch.bfloat16).double(), values)                          # both formats fit bf16
+    assert table[1] > 0 and (fmt != E4M3 or table[-1] == 448) and (fmt != E5M2 or table[-1] == 57344)
+
+
+def test_sgd_exact_hyper_parameters_keep_the_update_fp32_representable():
+    """Largest K of the gemm_update tests (4096), the largest |z| integer operands in [-4, 4] can
+    give (16 K) and every p0 in multiples of 1/8 within [-4, 4]: each intermediate of the SGD formula
+    is a multiple of 2^-12 below 2^12, so fp32 (and any FMA contraction of it) computes it exactly."""
+    K = 4096
+    g = torch.tensor([-16.0 * K, -16.0 * K + 1, -1.0, 0.0, 1.0, 777.0, 16.0 * K - 1, 16.0 * K], dtype=torch.float64)
+    p0 = torch.arange(-32, 33, dtype=torch.float64) / 8
+    gg, pp = torch.meshgrid(g, p0, indexing="ij")
+    w = torch.ones_like(gg, dtype=torch.bool)
+    hp = dict(adam=False, b1=0.0, b2=0.0, eps=0.0, bc1=1.0, bc2s=1.0, **SGD_EXACT)
+    r64, _, _ = opt_update_reference(pp, gg, None, None, w, torch.float64, **hp)
+    r32, _, _ = opt_update_reference(pp, gg, None, None, w, torch.float32, **hp)
+    assert torch.equal(r64, pp - SGD_EXACT["lr"] * (gg * SGD_EXACT["grad_scale"] + 2 * SGD_EXACT["l2"] * pp))
+    assert torch.equal(r64.float().double(), r64) and torch.equal(r32.double(), r64)
+    for part in (gg * SGD_EXACT["grad_scale"], 2 * SGD_EXACT["l2"] * pp, gg * SGD_EXACT["grad_scale"] + 2 * SGD_EXACT["l2"] * pp,
+                 SGD_EXACT["lr"] * (gg * SGD_EXACT["grad_scale"] + 2 * SGD_EXACT["l2"] * pp)):
+        assert torch.equal(part.float().double(), part)
+    assert torch.equal(r64 * 4096, (r64 * 4096).round()) and r64.abs().max() < 2 ** 12
+
+
+def test_claimed_split_factors_follow_the_restated_rules():
+    for (M, N, K), b_kc, split in FP8_SPLIT_CASES:
+        assert gemm_split_plan(M, N, K, fp8=True, b_kc=b_kc) == split, (M, N, K, b_kc)
+    for (M, N, K), split in UPDATE_SPLIT_CASES:
+        assert gemm_split_plan(M, N, K) == split, (M, N, K)
+    for s0, s1, K, split in PAIR_SPLIT_CASES:
+        assert gemm_pair_split_plan(s0, s1, K) == gemm_pair_split_plan(s1, s0, K) == split, (s0, s1, K)
+    assert {c[-1] for c in PAIR_SPLIT_CASES} == {1, 2, 4, 8}
+    # by hand: 60 tiles x 4 slices = 240 workgroups of 64 / 4 = 16 fp8 K steps; bf16 K steps are 32 deep
+    assert gemm_split_plan(1536, 2560, 4096, fp8=True) == 4 and gemm_split_plan(1536, 2560, 4096) == 4
+    assert gemm_split_plan(1536, 2560, 2048, fp8=True) == 1 and gemm_split_plan(4096, 3840, 8192) == 1
+    assert gemm_pair_split_plan((256, 512), (512, 256), 8192) == 8 and gemm_pair_split_plan((256, 512), (512, 256), 4096) == 1

@@ -681,6 +681,10 @@ def test_gemm_split_k_matches_reference(native_lib, M, N, K, a_kc, b_kc, out):
 
 
 def test_gemm_fp8_split_k(native_lib):
+    """A skinny fp8 forward with both operands K-contiguous. Despite the name it does not split:
+    gemm_split returns 1 for fp8 GEMMs with a K-contiguous B (they run better as 128x128 tiles), so
+    32 x 4 = 128 tiles of 256 < 240 take VAR 8's 128x128 ReLU-stage kernel in one pass. (The fp8
+    GEMMs that do split, VAR 14 and 15, are in test_gemm_fp8_exact_gpu.py.)"""
     f8 = torch.float8_e4m3fn
     M, N, K = 8192, 1024, 8192
     x8 = torch.randn(M, K, device=DEV).to(f8)
@@ -688,6 +692,7 @@ def test_gemm_fp8_split_k(native_lib):
     one = torch.ones(1, device=DEV)
     y = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
     PF.gemm(x8, True, w8, True, y, mode=PF.EPI_FWD, epi=PF.epi_spec(), scale_a=one, scale_b=one)
+    assert PF.gemm_last_kernel() == "mfma/var8/128x128/ek2/split1"
     ref = x8.double() @ w8.double().t()
     assert (y.double() - ref).abs().max().item() < 0.01 * ref.abs().max().item()
 
