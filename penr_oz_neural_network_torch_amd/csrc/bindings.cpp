@@ -479,9 +479,9 @@ void gemm_pair_op(const Tensor& A0, const Tensor& B0, const Tensor& C0, const Te
 }
 
 int64_t gemm_path_op(const Tensor& A, bool a_kc, const Tensor& B, bool b_kc, const Tensor& C, int64_t M, int64_t N,
-                     int64_t K) {
+                     int64_t K, bool force_generic) {
   auto p = gemm_args(A, a_kc, B, b_kc, C, c10::nullopt, c10::nullopt, c10::nullopt, 0, {}, {}, 1.0, false, M, N, K, 0,
-                     false, c10::nullopt);
+                     force_generic, c10::nullopt);
   return pz::gemm_path(p);
 }
 
@@ -1457,7 +1457,8 @@ TORCH_LIBRARY(pz, m) {
         "Tensor(a!) params, Tensor(b!)? exp_avg, Tensor(c!)? exp_avg_sq, Tensor(d!)? shadow, Tensor(e!)? stats, "
         "Tensor(f!)? amax, bool adam, float lr, float beta1, float beta2, float eps, float bias_c1, "
         "float bias_c2_sqrt, float grad_scale, float l2, Tensor? hp=None, Tensor? epoch=None, int stats_every=1) -> ()");
-  m.def("gemm_path(Tensor A, bool a_kc, Tensor B, bool b_kc, Tensor C, int M, int N, int K) -> int");
+  m.def("gemm_path(Tensor A, bool a_kc, Tensor B, bool b_kc, Tensor C, int M, int N, int K, "
+        "bool force_generic=False) -> int");
   m.def("gemm_skinny(Tensor x, Tensor w, Tensor(a!) out, Tensor? bias, int act) -> ()");
   m.def("gemm_skinny_eligible(Tensor x, Tensor w, Tensor out) -> bool");
   m.def("gemm_skinny_w8(Tensor x, Tensor w8, Tensor scale, Tensor(a!) out, Tensor? bias, int act) -> ()");

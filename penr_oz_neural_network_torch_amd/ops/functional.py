@@ -176,10 +176,11 @@ def relu_mask_pack(y_pos: Tensor) -> Tensor:
     return blocked.contiguous().reshape(rows, ld)
 
 
-def gemm_path(a: Tensor, a_kc: bool, b: Tensor, b_kc: bool, out: Tensor) -> str:
+def gemm_path(a: Tensor, a_kc: bool, b: Tensor, b_kc: bool, out: Tensor, force_generic: bool = False) -> str:
+    """The kernel family :func:`gemm` would dispatch these operands to, without launching anything."""
     M, N = out.shape
     K = a.shape[1] if a_kc else a.shape[0]
-    path = _ops().gemm_path(a, a_kc, b, b_kc, out, M, N, K)
+    path = _ops().gemm_path(a, a_kc, b, b_kc, out, M, N, K, force_generic)
     return {1: "mfma", 2: "mfma_wide"}.get(path, "generic")  # mfma_wide: fp32 / fp64 matrix cores
 
 

@@ -192,14 +192,19 @@ def histogram_reference(values, lo: float, hi: float, bins: int) -> np.ndarray:
 
 
 # ------------------------------------------------------------------------------------ exact GEMM
-def exact_operands(M: int, N: int, K: int, a_kc: bool, b_kc: bool, seed: int):
-    """bf16 ``a`` ([M, K] if ``a_kc`` else [K, M]) and ``b`` ([N, K] if ``b_kc`` else [K, N]) with
-    integer entries in [-4, 4] from a CPU generator, and the fp64 ``z = op(a) @ op(b)``. Every
-    partial sum of ``z`` is an integer below 16 K < 2^24, so every fp32 accumulation order gives ``z``."""
-    assert K * 16 < 2 ** 24
+def exact_operands(M: int, N: int, K: int, a_kc: bool, b_kc: bool, seed: int, dtype=torch.bfloat16, hi: int = 4):
+    """``a`` ([M, K] if ``a_kc`` else [K, M]) and ``b`` ([N, K] if ``b_kc`` else [K, N]) in ``dtype``
+    (bf16, fp32 or fp64) with integer entries in [-hi, hi] from a CPU generator, and the fp64
+    ``z = op(a) @ op(b)``. Every partial sum of ``z`` is an integer below K hi^2, which must stay
+    under 2^24 (bf16 / fp32 operands: every fp32 accumulation order gives ``z``) or 2^53 (fp64
+    operands: every fp64 order does, the reference's own matmul included). bf16 holds the integers up
+    to 256."""
+    assert dtype in (torch.bfloat16, torch.float32, torch.float64) and hi >= 1
+    assert K * hi * hi < (2 ** 53 if dtype == torch.float64 else 2 ** 24)
+    assert dtype != torch.bfloat16 or hi <= 256
     g = torch.Generator(device="cpu").manual_seed(seed)
-    a = torch.randint(-4, 5, (M, K) if a_kc else (K, M), generator=g).to(torch.bfloat16)
-    b = torch.randint(-4, 5, (N, K) if b_kc else (K, N), generator=g).to(torch.bfloat16)
+    a = torch.randint(-hi, hi + 1, (M, K) if a_kc else (K, M), generator=g).to(dtype)
+    b = torch.randint(-hi, hi + 1, (N, K) if b_kc else (K, N), generator=g).to(dtype)
     return a, b, (a.double() if a_kc else a.double().t()) @ (b.double().t() if b_kc else b.double())
 
 
@@ -232,8 +237,17 @@ def gemm_epilogue_reference(z: torch.Tensor, *, alpha: float, bias, mode: int, a
 def assert_gemm_exact(out: torch.Tensor, ref64: torch.Tensor) -> None:
     """``out`` holds exactly the fp64 reference rounded once to its dtype. The reference must be
     fp32-representable (the kernels' epilogue math is fp32: only then is "exact" meaningful); the
-    comparison is by value, so -0 equals +0."""
+    comparison is by value, so -0 equals +0. An fp64 ``out`` (the fp64 kernels' epilogue math is
+    fp64) must equal ``ref64`` itself, which then need not fit fp32."""
     assert torch.isfinite(out).all()
+    if out.dtype == torch.float64:
+        assert ref64.dtype == torch.float64
+        if not torch.equal(out, ref64):
+            bad = out != ref64
+            i = bad.nonzero()[0].tolist()
+            raise AssertionError(f"{int(bad.sum())} of {bad.numel()} elements differ; first at {i}: "
+                                 f"{out[tuple(i)].item()!r} != {ref64[tuple(i)].item()!r}")
+        return
     assert torch.equal(ref64.float().double(), ref64), "the reference is not exact in fp32"
     want = ref64.float().to(out.dtype)
     if not torch.equal(out.float(), want.float()):

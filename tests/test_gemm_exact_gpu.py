@@ -29,7 +29,10 @@ Dispatch cells reached (kFill = 240):
   mfma/var30/256x256/ek*/split8     Ssplit (1536, 1280, 4096): forward, dX, dW (fp32 accumulate: the last
                                     arriver's read-modify-write)
   mfma/var6/256x256/ek0/split8      Ssplit with ragged M (1528, 1280, 4096)
-  generic/var0/64x64/ek0/split1     (67, 45, 23) forced, bf16 and fp32 operands; bf16 out + accumulate at S128
+  generic/var0/64x64/ek0/split1     (67, 45, 23) forced, bf16 and fp32 operands; bf16 out + accumulate at S128;
+                                    fp64 operands with fp64 C, bias, aux and column sums there and at (9, 9, 9)
+                                    (fp64 bounds: run_case; the fp32 / fp64 matrix-core kernel runs through
+                                    run_case from test_gemm_wide_exact_gpu.py)
   sk/var0/256x256/ek1|3|4|5|6|100    (1536, 1280, 512) on 37 CUs (30 data-parallel tiles) and 200 (two K halves)
 Not reached on purpose: the !buffer_ok fallbacks (VAR 0; need a 4 GiB operand), fp32 outputs of the
 stream-K engine outside the dW layout (it has none). fp8 operands run through this file's run_case
@@ -190,10 +193,11 @@ def expected_kernel(cls: str, form: str, no_split: bool = False) -> str:
 
 # ------------------------------------------------------------------------------------ inputs
 @functools.lru_cache(maxsize=None)
-def operands(M, N, K, a_kc, b_kc, fmts=None):
-    """Integer operands on the device: bf16, or (``fmts`` = the two fp8 formats) fp8."""
+def operands(M, N, K, a_kc, b_kc, fmts=None, dtype=BF16, hi=4):
+    """Integer operands in [-hi, hi] on the device: ``dtype``, or (``fmts`` = the two fp8 formats) fp8."""
     seed = M + 3 * N + 7 * K + 2 * a_kc + b_kc
-    a, b, z = exact_operands(M, N, K, a_kc, b_kc, seed) if fmts is None else exact_operands_fp8(M, N, K, a_kc, b_kc, *fmts, seed)
+    a, b, z = (exact_operands(M, N, K, a_kc, b_kc, seed, dtype, hi) if fmts is None
+               else exact_operands_fp8(M, N, K, a_kc, b_kc, *fmts, seed))
     return a.to(DEV), b.to(DEV), z.to(DEV)
 
 
@@ -217,15 +221,16 @@ def bias_vec(N):
 
 
 @functools.lru_cache(maxsize=None)
-def stage_source(M, N, act, y_scale):
+def stage_source(M, N, act, y_scale, dtype=BF16):
     """What a backward epilogue reads of the stage it differentiates: ReLU -> random bits (y > 0) and
-    an integer-valued y with that sign pattern; sigmoid / tanh -> a stored bf16 y = act(u) * y_scale."""
+    an integer-valued y with that sign pattern; sigmoid / tanh -> a stored y = act(u) * y_scale,
+    rounded once to ``dtype``."""
     g = torch.Generator(device="cpu").manual_seed(M * 31 + N + act)
     if act == RELU:
-        y = torch.randint(-3, 4, (M, N), generator=g).to(DEV, BF16)
+        y = torch.randint(-3, 4, (M, N), generator=g).to(DEV, dtype)
         return y, y > 0
     u = torch.randn(M, N, generator=g, dtype=F64)
-    return ((torch.sigmoid(u) if act == SIGM else torch.tanh(u)) * y_scale).to(DEV, BF16), None
+    return ((torch.sigmoid(u) if act == SIGM else torch.tanh(u)) * y_scale).to(DEV, dtype), None
 
 
 @functools.lru_cache(maxsize=None)
@@ -234,14 +239,16 @@ def old_c(M, N):
     return torch.randint(-64, 65, (M, N), generator=g).to(DEV, F32)
 
 
-def framed(rows, cols, dtype, strided, fill=7.0, src=None, pad=8):
+def framed(rows, cols, dtype, strided, fill=7.0, src=None, pad=8, odd=0):
     """A [rows, cols] tensor: contiguous, or (``strided``) the column slice [:, pad : pad + cols] of a
-    tensor 2 pad columns wider and 8 rows taller. Returns (view, base); everything is ``fill`` (then ``src``)."""
+    tensor 2 pad + odd columns wider and 8 rows taller. Returns (view, base); everything is ``fill``
+    (then ``src``). pad = 1 with an odd width puts an fp32 / fp64 view's first element 4 / 8 bytes
+    past a 16-byte boundary and its rows a stride apart that is no multiple of 16 bytes."""
     if not strided:
         base = torch.full((rows, cols), fill, device=DEV, dtype=F32).to(dtype)
         view = base
     else:
-        base = torch.full((rows + 8, cols + 2 * pad), fill, device=DEV, dtype=F32).to(dtype)
+        base = torch.full((rows + 8, cols + 2 * pad + odd), fill, device=DEV, dtype=F32).to(dtype)
         view = base[:rows, pad:pad + cols]
     if src is not None:
         view.copy_(src)
@@ -253,7 +260,8 @@ def frame_untouched(view, base, fill=7.0):
     if view is base:
         return True
     pad = view.storage_offset() - base.storage_offset()
-    probe = base.float()
+    # (always a copy: .float() of an fp32 base is the base itself, and would be overwritten below)
+    probe = base.clone() if base.dtype == F64 else base.float().double()
     probe[:view.shape[0], pad:pad + view.shape[1]] = fill
     return bool((probe == fill).all())
 
@@ -299,19 +307,59 @@ def dev_scalar(v):
     return torch.tensor([v], device=DEV)
 
 
+U64 = 2.0 ** -53
+# fp64 operands, sigmoid / tanh forward: bound on |y - ref| in units of 2^-53 |ref|, ref = torch's fp64
+# CPU result on the same (exact) h. The device exp / tanh are the only steps whose error is not derived:
+# 4 x the worst measured on MI355X, 8.001 (tanh; sigmoid 3.567), wide and generic kernel alike. A
+# figure above 16 would be a finding, not a reason to widen this.
+F64_FWD_ACT_ULPS = 32.0
+# fp64 operands, sigmoid / tanh backward from an fp64 aux, in units of 2^-53 |g| scale_pre scale_post
+# (run_case's docstring derives it)
+F64_BWD_ACT_ULPS = 16.0
+
+
 def run_case(shape, form, p=0.5, *, engine=1, cus=0, force_generic=False, no_split=False, strided=False,
-             idx_ld=0, in_dtype=BF16, out_dtype=None, store_c=True, layout=None, fmts=None, q8="std"):
+             idx_ld=0, in_dtype=BF16, out_dtype=None, store_c=True, layout=None, fmts=None, q8="std",
+             bias_dtype=F32, colsum_dtype=F32, aux_dtype=None, hi=4, pad=None, odd=0):
     """One GEMM launch of ``form`` checked against the fp64 reference. Returns what it produced.
     ``fmts`` = (format of A, format of B): fp8 operands in layout ``layout`` (default: the form's),
     dequantised by F8_SCALES (folded into the reference's alpha; the kernel's alpha is raised by as
     much, so that every form sees the values the bf16 run sees). ``q8``: which OUT8_Q factor the
-    fp8 copy takes ("std": 2^-3, at which e4m3 saturates too)."""
+    fp8 copy takes ("std": 2^-3, at which e4m3 saturates too).
+
+    ``in_dtype`` fp32 / fp64 (gemm_wide.hip, gemm_generic.hip): ``hi`` = the operands' integer range
+    (they are generated in ``in_dtype``), ``bias_dtype`` / ``colsum_dtype`` fp32 or fp64,
+    ``aux_dtype`` = the stored stage output's type (given: y is rounded once to it, not to bf16 first),
+    ``pad`` / ``odd`` = the frame of the strided views of A, B, C and aux (see framed); these
+    operands never take the bf16 kernels' ReLU bitmask.
+
+    fp64 operands run the epilogue in fp64 (u = 2^-53), so the exact forms must equal the reference
+    in an fp64 C, and the others get fp64 bounds (+ one rounding of an fp32 / bf16 C):
+      * p = 0.3, none / ReLU: exact zero pattern, kept values within 4 u |ref|: at most two
+        multiplications by the double 1/(1-p) in the kernel (epi_scale<double>) and in the reference.
+        The same reference with that scale rounded to fp32 must break the bound somewhere (asserted:
+        otherwise the test could not tell which scale the kernel took).
+      * sigmoid / tanh forward: F64_FWD_ACT_ULPS u |ref| against torch's fp64 CPU activations.
+      * sigmoid / tanh backward from an fp64 aux y: F64_BWD_ACT_ULPS u |g| scale_pre scale_post.
+        Let s = fl(1 / (1 - p)), i = fl(1 - p) (the spec's two doubles), a* = y i, d* = act'(a*) and
+        T = g s d* s in real arithmetic; |a*| <= 1 (asserted), so a*^2 <= 1 and d* <= 1. epi_bwd:
+        a = fl(y i) = a* (1 + e); tanh d = fl(1 - fl(a a)) is within (2 + 1) u a*^2 + u d* <= 4 u of
+        d*, sigmoid d = fl(a fl(1 - a)) within 3 u d* + u a*^2 <= 1.75 u; then g1 = fl(g s),
+        g2 = fl(g1 d), g3 = fl(g2 s) add 3 u d: |out - T| <= 7 u |g| s^2. The reference
+        (stage_bwd_reference, on the CPU) divides: a' = fl(y / s) with s = (1 / i)(1 + e1) is within
+        2 u of a*, so d' is within (4 + 1) u + u = 6 u of d*, and its three multiplications add
+        3 u: |ref - T| <= 9 u |g| s^2. Together 16 u |g| s^2, with one dropout or none less.
+      * column sums: M u_cs sum|ref| + the sum of the per-element bounds, u_cs = 2^-53 for an fp64
+        colsum; on the exact forms they equal the reference's (every partial sum is exact)."""
     M, N, K = shape
     f = FORMS[form]
     a_kc, b_kc = LAYOUTS[layout or f.layout]
-    a0, b0, z = operands(M, N, K, a_kc, b_kc, fmts)
+    a0, b0, z = operands(M, N, K, a_kc, b_kc, fmts, in_dtype if fmts is None else BF16, hi)
     out_dtype = out_dtype or f.out
+    f64 = in_dtype == F64
     what = f"{form} {shape} p={p}"
+    if in_dtype != BF16:
+        what += f" {str(in_dtype)[6:]}->{str(out_dtype)[6:]}" + (" generic" if force_generic else "")
     alpha = alpha_of(f, K)
     k_alpha, scales = alpha, {}
     if fmts is not None:
@@ -323,25 +371,39 @@ def run_case(shape, form, p=0.5, *, engine=1, cus=0, force_generic=False, no_spl
     kq = keep(M, N, ld, LID_POST, p) if f.post else None
     epi = PF.NO_EPI if f.mode == PF.EPI_STORE else PF.epi_spec(f.act, LID_PRE if f.pre else -1,
                                                                 LID_POST if f.post else -1, p, SEED)
-    bias = bias_vec(N) if f.bias else None
+    bias = bias_vec(N).to(bias_dtype) if f.bias else None
     # (fp8 operands: 16-byte aligned slices of rows that are a multiple of 16 bytes apart)
-    a, _ = framed(*a0.shape, in_dtype if fmts is None else fmts[0], strided, src=a0, pad=8 if fmts is None else 16)
-    b, _ = framed(*b0.shape, in_dtype if fmts is None else fmts[1], strided, src=b0, pad=8 if fmts is None else 16)
+    opad, cpad = pad or (8 if fmts is None else 16), pad or 8
+    a, _ = framed(*a0.shape, in_dtype if fmts is None else fmts[0], strided, src=a0, pad=opad, odd=odd)
+    b, _ = framed(*b0.shape, in_dtype if fmts is None else fmts[1], strided, src=b0, pad=opad, odd=odd)
     aux = bits = mask = aux_v = aux_base = None
     if f.mode == PF.EPI_BWD:
-        y_src, bits = stage_source(M, N, f.act, scale if f.post else 1.0)
+        y_src, bits = stage_source(M, N, f.act, scale if f.post else 1.0, aux_dtype or BF16)
         if f.mask:
             mask = PF.relu_mask_pack(bits)
         else:
-            aux, bits = y_src.to(out_dtype), None
-            aux_v, aux_base = framed(M, N, out_dtype, strided, src=aux)
-    elif f.mask and not force_generic:
+            aux, bits = y_src.to(aux_dtype or out_dtype), None
+            aux_v, aux_base = framed(M, N, aux.dtype, strided, src=aux, pad=cpad, odd=odd)
+    elif f.mask and not force_generic and in_dtype == BF16:
         mask = torch.full(PF.relu_mask_shape(M, N), 0xAB, device=DEV, dtype=torch.uint8)
     c_old = old_c(M, N) if f.accumulate else None
-    ref, cs_ref = gemm_epilogue_reference(z, alpha=alpha, bias=bias, mode=f.mode, act=f.act, keep_pre=kp, keep_post=kq,
-                                          scale=scale, aux=aux, bits=bits, c_old=c_old)
-    c, c_base = framed(M, N, out_dtype, strided, fill=7.0 if (strided or not store_c) else float("nan"), src=c_old)
-    colsum = torch.zeros(N, device=DEV) if f.colsum else None
+    # fp64 sigmoid / tanh stages: the reference runs on the CPU (the device's own exp, tanh and
+    # division are what is under test)
+    host = f64 and f.act in (SIGM, TANH) and f.mode != PF.EPI_STORE
+
+    def reference(sc):
+        on = (lambda t: None if t is None else t.cpu()) if host else (lambda t: t)
+        r, cs = gemm_epilogue_reference(on(z), alpha=alpha, bias=on(bias), mode=f.mode, act=f.act, keep_pre=on(kp),
+                                        keep_post=on(kq), scale=sc, aux=on(aux), bits=on(bits), c_old=on(c_old))
+        return r.to(DEV), cs.to(DEV)
+
+    ref, cs_ref = reference(scale)
+    c, c_base = framed(M, N, out_dtype, strided, fill=7.0 if (strided or not store_c) else float("nan"), src=c_old,
+                       pad=cpad, odd=odd)
+    if strided and pad == 1:  # off the 16-byte vector path: base and row stride
+        for t in (a, b, c) + (() if aux_v is None else (aux_v,)):
+            assert t.data_ptr() % 16 != 0 and (t.stride(0) * t.element_size()) % 16 != 0, what
+    colsum = torch.zeros(N, device=DEV, dtype=colsum_dtype) if f.colsum else None
     fmt = E5M2 if f.mode == PF.EPI_BWD else E4M3
     o8 = o8_base = qs = amax = None
     rule8, q8 = OUT8_Q[fmt], OUT8_Q[fmt][q8]
@@ -358,6 +420,20 @@ def run_case(shape, form, p=0.5, *, engine=1, cus=0, force_generic=False, no_spl
     exact = f.act in (NONE, RELU) and (not f.drop or p in (0.5, 1.0))
     total = (scale if f.pre else 1.0) * (scale if f.post else 1.0)
     g_abs = (z * alpha).abs()
+    # fp64 math: the per-element bound of each non-exact group, and one rounding of x to the output
+    # type on top, |fl(x) - ref| <= |x - ref| + u_out |x|
+    u_out = {BF16: 2.0 ** -8, F32: U32, F64: 0.0}[out_dtype] * (1 + 2.0 ** -40)
+    elem64 = None
+    if f64 and not exact:
+        if f.act in (NONE, RELU):
+            elem64 = 4 * U64 * ref.abs()
+            if out_dtype == F64:
+                assert ((reference(torch.tensor(scale, dtype=F32).item())[0] - ref).abs() > elem64).any(), what
+        elif f.mode == PF.EPI_FWD:
+            elem64 = F64_FWD_ACT_ULPS * U64 * ref.abs()
+        else:
+            assert aux.dtype == F64 and (aux.abs() * (1.0 - p if f.post else 1.0) <= 1).all(), what
+            elem64 = F64_BWD_ACT_ULPS * U64 * g_abs * total
     if not store_c:
         assert (c_base.float() == 7.0).all(), what
         y = ref.float().to(out_dtype)  # (store_c = False runs at p = 0.5 only: the stored value is known)
@@ -369,23 +445,39 @@ def run_case(shape, form, p=0.5, *, engine=1, cus=0, force_generic=False, no_spl
         elif f.act in (NONE, RELU):  # p = 0.3: the zero pattern is exact, kept values carry the scale's rounding
             assert torch.isfinite(c).all(), what
             assert torch.equal(c == 0, ref == 0), what
-            within(c, ref, 2.0 ** -8 * ref.abs() if out_dtype == BF16 else 4 * U32 * ref.abs(), "scaled " + what)
+            if f64:
+                within(c, ref, elem64 + u_out * ref.abs(), "scaled64 " + what)
+            else:
+                within(c, ref, 2.0 ** -8 * ref.abs() if out_dtype == BF16 else 4 * U32 * ref.abs(), "scaled " + what)
         elif f.mode == PF.EPI_FWD:
-            within(c, ref, (2.0 ** -8 if out_dtype == BF16 else 1e-5) * ref.abs() + 1e-5, "fwd_act " + what)
+            if f64:
+                if out_dtype == F64:
+                    ulps = ((c - ref).abs() / (U64 * ref.abs().clamp_min(1e-300))).max().item()
+                    print(f"fwd_act64 {what}: worst |err| / (2^-53 max(|ref|, tiny)) = {ulps:.3f}")
+                within(c, ref, elem64 + u_out * ref.abs(), "fwd_act64 " + what)
+            else:
+                within(c, ref, (2.0 ** -8 if out_dtype == BF16 else 1e-5) * ref.abs() + 1e-5, "fwd_act " + what)
             if kq is not None:
                 assert (c[~kq] == 0).all(), what
         else:
-            bound = 1e-5 * ref.abs() + 4 * U32 * g_abs * total + (2.0 ** -8 * ref.abs() if out_dtype == BF16 else 0.0)
-            within(c, ref, bound, "bwd_act " + what)
+            if f64:
+                bound = elem64 + u_out * ref.abs()
+            else:
+                bound = 1e-5 * ref.abs() + 4 * U32 * g_abs * total + (2.0 ** -8 * ref.abs() if out_dtype == BF16 else 0.0)
+            within(c, ref, bound, ("bwd_act64 " if f64 else "bwd_act ") + what)
             assert (c[~(kp & kq)] == 0).all(), what
         assert frame_untouched(c, c_base), what
     if aux_v is not None:
         assert frame_untouched(aux_v, aux_base) and torch.equal(aux_v, aux), what
     if colsum is not None:
         abs_sum = ref.abs().sum(0)
+        u_cs = U64 if colsum_dtype == F64 else U32
         if exact:
-            assert abs_sum.max().item() / min(alpha, 1.0) < 2 ** 24  # every partial sum is exact in fp32
+            # every partial sum is exact in the colsum's type (and in the fp64 kernels' fp64 partial sums)
+            assert abs_sum.max().item() / min(alpha, 1.0) < (2 ** 53 if colsum_dtype == F64 else 2 ** 24)
             assert torch.equal(colsum.double(), cs_ref), (what, (colsum.double() - cs_ref).abs().max().item())
+        elif f64:
+            within(colsum, cs_ref, M * u_cs * abs_sum + elem64.sum(0), "colsum64 " + what)
         elif f.act in (NONE, RELU):
             within(colsum, cs_ref, (M + 3) * U32 * abs_sum, "colsum_scaled " + what)
         else:
@@ -490,15 +582,23 @@ GENERIC_FORMS = ([f for f in FWD_FORMS if not FORMS[f].out8] + ["fwd_acc", "dx_p
                  "dx_sigmoid_aux", "dx_tanh_aux", "dw_f32", "dw_f32_acc", "tn_f32"])
 
 
-@pytest.mark.parametrize("in_dtype", [BF16, F32], ids=["bf16", "f32"])
+GENERIC_TTT = (9, 9, 9)   # the reference project's own tic-tac-toe layers
+
+
+@pytest.mark.parametrize("in_dtype", [BF16, F32, F64], ids=["bf16", "f32", "f64"])
 @pytest.mark.parametrize("form", GENERIC_FORMS)
 def test_generic_kernel_is_exact(native_lib, form, in_dtype):
     """gemm_generic.hip at a shape with no aligned dimension: bf16 operands with the form's output
-    type, fp32 operands with fp32 outputs (aux in the output type)."""
-    for p in FORMS[form].p:
-        r = run_case(GENERIC, form, p, force_generic=True, in_dtype=in_dtype, out_dtype=F32 if in_dtype == F32 else None)
-        print(f"generic {form} p={p}: -0 stored: {r.neg0}")
-        assert r.name == "generic/var0/64x64/ek0/split1"
+    type, fp32 operands with fp32 outputs (aux in the output type); fp64 operands (the <double, double>
+    instantiation, also at the 9-wide shape) with fp64 outputs, bias, aux and column sums."""
+    kw = dict(out_dtype=F32) if in_dtype == F32 else {}
+    if in_dtype == F64:
+        kw = dict(out_dtype=F64, bias_dtype=F64, aux_dtype=F64, colsum_dtype=F64)
+    for shape in (GENERIC, GENERIC_TTT) if in_dtype == F64 else (GENERIC,):
+        for p in FORMS[form].p:
+            r = run_case(shape, form, p, force_generic=True, in_dtype=in_dtype, **kw)
+            print(f"generic {shape} {form} p={p}: -0 stored: {r.neg0}")
+            assert r.name == "generic/var0/64x64/ek0/split1"
 
 
 def test_bf16_accumulate_takes_the_generic_kernel(native_lib):

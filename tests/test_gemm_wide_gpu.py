@@ -72,8 +72,11 @@ def test_gemm_wide_epilogues_match_generic(native_lib, dtype):
     m1 = torch.from_numpy(keep_mask(M * N, *seed, 3, p).reshape(M, N)).to(DEV)
     m2 = torch.from_numpy(keep_mask(M * N, *seed, 4, p).reshape(M, N)).to(DEV)
     ref = torch.relu(h * m1 / (1 - p)) * m2 / (1 - p)
-    # (the stage's dropout scale 1/(1-p) is an fp32 constant of the epilogue spec: ~6e-8 relative)
-    assert (outs[0].double() - ref).abs().max().item() < max(tol, 2e-7) * ref.abs().max().item()
+    # (the fp64 kernels take the stage's dropout scale 1/(1-p) as a double, epi_scale<double>: an
+    # fp32-rounded scale, 3e-8 relative at p = 0.25, fails the fp64 bound. A max-norm bound, since
+    # these random operands carry summation error through the stage; test_gemm_wide_exact_gpu.py
+    # checks the stage element by element on exact operands)
+    assert (outs[0].double() - ref).abs().max().item() < tol * ref.abs().max().item()
     # backward stage: dZ = epi_bwd(g_a @ Wᵀ, y) with column sums
     ga, wt = _operands(M, K, N, True, True, dtype, 8)  # [M, N] and [K, N]: dX = ga @ wtᵀ -> [M, K]
     y = torch.tanh(torch.randn(M, K, device=DEV, dtype=dtype))

@@ -150,6 +150,90 @@ def test_assert_gemm_exact_demands_an_fp32_exact_reference_and_equal_values():
         assert_gemm_exact(nan, ref)
 
 
+@pytest.mark.parametrize("dtype,hi", [(torch.float32, 256), (torch.float64, 2 ** 20), (torch.float64, 4), (torch.bfloat16, 256)])
+@pytest.mark.parametrize("a_kc,b_kc", [(True, False), (False, True)])
+def test_widened_exact_operands_match_python_int_dot_products(dtype, hi, a_kc, b_kc):
+    M, N, K = 19, 23, 96
+    a, b, z = exact_operands(M, N, K, a_kc, b_kc, seed=7, dtype=dtype, hi=hi)
+    assert a.dtype == b.dtype == dtype and z.dtype == torch.float64 and z.shape == (M, N)
+    al, bl = a.double().tolist(), b.double().tolist()
+    assert all(float(v).is_integer() and abs(v) <= hi for row in al + bl for v in row)
+    assert max(abs(v) for row in al for v in row) > hi * 0.9      # the range is used
+    for m, n in [(0, 0), (M - 1, N - 1), (3, 17), (18, 0), (11, 22)]:
+        dot = sum(int(al[m][k] if a_kc else al[k][m]) * int(bl[n][k] if b_kc else bl[k][n]) for k in range(K))
+        assert z[m, n].item() == dot and int(z[m, n].item()) == dot
+    if hi == 4:  # the default range draws the same integers in every dtype
+        assert torch.equal(a, exact_operands(M, N, K, a_kc, b_kc, seed=7)[0].to(dtype))
+    # the limits: K hi^2 below 2^24 (bf16, fp32) or 2^53 (fp64); bf16 holds integers up to 256
+    exact_operands(4, 4, 255, a_kc, b_kc, seed=1, dtype=torch.float32, hi=256)
+    with pytest.raises(AssertionError):
+        exact_operands(4, 4, 256, a_kc, b_kc, seed=1, dtype=torch.float32, hi=256)
+    exact_operands(4, 4, 2 ** 12, a_kc, b_kc, seed=1, dtype=torch.float64, hi=2 ** 20)
+    with pytest.raises(AssertionError):
+        exact_operands(4, 4, 2 ** 13, a_kc, b_kc, seed=1, dtype=torch.float64, hi=2 ** 20)
+    with pytest.raises(AssertionError):
+        exact_operands(4, 4, 16, a_kc, b_kc, seed=1, dtype=torch.bfloat16, hi=257)
+
+
+def test_assert_gemm_exact_fp64_outputs_equal_the_reference_itself():
+    _, _, z = exact_operands(16, 24, 64, True, False, seed=2, dtype=torch.float64, hi=2 ** 20)
+    third = torch.full((24,), 1 / 3, dtype=torch.float64)
+    ref, _ = gemm_epilogue_reference(z, alpha=0.5, bias=third, mode=0, act=0, keep_pre=None, keep_post=None, scale=1.0)
+    assert not torch.equal(ref.float().double(), ref)     # not fp32-representable: fine for an fp64 output
+    assert_gemm_exact(ref.clone(), ref)
+    zero = ref.clone()
+    zero[2, 2] = 0.0
+    neg = zero.clone()
+    neg[2, 2] = -0.0
+    assert_gemm_exact(neg, zero)                          # by value: -0 equals +0
+    for direction in (float("inf"), -float("inf")):       # one ulp either way is rejected
+        off = ref.clone()
+        off[3, 5] = torch.nextafter(off[3, 5], torch.tensor(direction, dtype=torch.float64))
+        assert off[3, 5] != ref[3, 5] and abs(off[3, 5] - ref[3, 5]) <= 2.0 ** -52 * abs(ref[3, 5])
+        with pytest.raises(AssertionError, match="1 of 384 elements differ"):
+            assert_gemm_exact(off, ref)
+    with pytest.raises(AssertionError, match="of 384 elements differ"):
+        assert_gemm_exact(ref.float().double(), ref)      # an fp32 round trip of the values is not equal
+    nan = ref.clone()
+    nan[0, 0] = float("nan")
+    with pytest.raises(AssertionError):
+        assert_gemm_exact(nan, ref)
+
+
+@pytest.mark.parametrize("act", [0, 1])
+def test_fp64_epilogue_reference_is_exact_at_half_dropout_and_tells_the_scales_apart_at_p03(act):
+    """p = 0.5: every step of the reference is exact in fp64 (checked against Python fractions).
+    p = 0.3: the reference with the scale rounded to fp32 leaves the 4 * 2^-53 |ref| band the fp64
+    GPU tests allow, on the shapes they use: those tests can tell which scale a kernel took."""
+    from fractions import Fraction
+    M, N, K = 9, 9, 9
+    _, _, z = exact_operands(M, N, K, True, False, seed=M + 3 * N + 7 * K + 2, dtype=torch.float64, hi=2 ** 20)
+    bias = (torch.arange(N, dtype=torch.float64) - 4) / 8
+    kp, kq = keep2d(M, N, N, (1, 2), 3, 0.5), keep2d(M, N, N, (1, 2), 4, 0.5)
+    ref, cs = gemm_epilogue_reference(z, alpha=0.5, bias=bias, mode=1, act=act, keep_pre=kp, keep_post=kq, scale=2.0)
+    for m in range(M):
+        for n in range(N):
+            h = Fraction(int(z[m, n].item())) / 2 + Fraction(int(bias[n].item() * 8), 8)
+            v = h * 2 if kp[m, n] else Fraction(0)
+            v = max(v, Fraction(0)) if act == 1 else v
+            v = v * 2 if kq[m, n] else Fraction(0)
+            assert Fraction(ref[m, n].item()) == v
+    assert all(Fraction(cs[n].item()) == sum(Fraction(ref[m, n].item()) for m in range(M)) for n in range(N))
+    p = 0.3
+    s64 = 1.0 / (1.0 - p)
+    s32 = torch.tensor(s64, dtype=torch.float32).item()
+    assert s32 != s64
+    for shape in [(200, 136, 96), (384, 640, 64), (67, 45, 23), (9, 9, 9)]:
+        M, N, K = shape
+        _, _, z = exact_operands(M, N, K, True, False, seed=M + 3 * N + 7 * K + 2)
+        kp, kq = keep2d(M, N, N, (1, 2), 3, p), keep2d(M, N, N, (1, 2), 4, p)
+        args = dict(alpha=0.5, bias=None, mode=1, act=act, keep_pre=kp, keep_post=kq)
+        ref, _ = gemm_epilogue_reference(z, scale=s64, **args)
+        ref32, _ = gemm_epilogue_reference(z, scale=s32, **args)
+        kept = ref != 0
+        assert kept.any() and ((ref32 - ref).abs() > 4 * 2.0 ** -53 * ref.abs())[kept].all()
+
+
 @pytest.mark.parametrize("act", [0, 1, 2, 3])
 @pytest.mark.parametrize("pre,post", [(False, False), (True, False), (False, True), (True, True)])
 def test_gemm_epilogue_reference_forward_is_the_stage_reference(act, pre, post):
