@@ -60,22 +60,6 @@ PZ_DEV void blds16(i32x4_t rs, uint32_t voff, uint32_t soff, uint32_t lds) {
 #undef PZ_BLDS
 }
 
-// 4-byte LDS-DMA used as an L2 PREFETCH: touching one dword of a 128-B line brings the line into
-// the XCD's L2 several ring steps before the real staging DMA asks for it; the bytes land in a
-// 256-B dummy LDS area nobody reads (no VGPR is written, so nothing can be clobbered)
-PZ_DEV void glds4(const void* gsrc, uint32_t lds) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dword %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds)
-      : "memory");
-}
-
 PZ_DEV i32x4_t buf_rsrc(const void* base) {
   const uint64_t b = reinterpret_cast<uint64_t>(base);
   i32x4_t r;
@@ -157,7 +141,7 @@ PZ_DEV i16x8_t frag_mn(const PZ_LDS char* tile, int col16, int kbase, int lane) 
 // offset is wave-uniform and rides in soffset — one (BK 32) or two (BK 64: the swizzle flips
 // with the piece's parity) per-lane offsets stay live instead of one per piece (the 16 of a
 // BK 64 K-contiguous pair of operands spilled to scratch inside the loop)
-template <int R, int NW, int BK = 32, bool BUF = false, int POL = 0, bool FULL = false>
+template <int R, int NW, int BK = 32, bool BUF = false, bool FULL = false>
 PZ_DEV void stage_kc(const uint16_t* __restrict__ g, int64_t ld, int row0, int rows_valid, int k0,
                      PZ_LDS char* tile, int wave, int lane, i32x4_t rs = {}) {
   constexpr int CPR = BK / 8;             // 16-B chunks per row
@@ -172,14 +156,14 @@ PZ_DEV void stage_kc(const uint16_t* __restrict__ g, int64_t ld, int row0, int r
     if constexpr (BUF && FULL) {
       const uint32_t voff = (static_cast<uint32_t>(lane / CPR) * static_cast<uint32_t>(ld) + chunk * 8) * 2u;
       const uint32_t soff = (static_cast<uint32_t>(row0 + rbase) * static_cast<uint32_t>(ld) + static_cast<uint32_t>(k0)) * 2u;
-      blds16<POL>(rs, voff, __builtin_amdgcn_readfirstlane(soff), lds_addr(tile + rbase * BK * 2));
+      blds16<0>(rs, voff, __builtin_amdgcn_readfirstlane(soff), lds_addr(tile + rbase * BK * 2));
       continue;
     }
     int gr = row0 + r;
     gr = gr < rows_valid ? gr : rows_valid - 1;
     if constexpr (BUF) {
       const uint32_t voff = (static_cast<uint32_t>(gr) * static_cast<uint32_t>(ld) + chunk * 8) * 2u;
-      blds16<POL>(rs, voff, __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(k0) * 2u), lds_addr(tile + rbase * BK * 2));
+      blds16<0>(rs, voff, __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(k0) * 2u), lds_addr(tile + rbase * BK * 2));
     } else {
       const uint16_t* src = g + static_cast<int64_t>(gr) * ld + k0 + chunk * 8;
       glds16(src, lds_addr(tile + rbase * BK * 2));
@@ -188,7 +172,7 @@ PZ_DEV void stage_kc(const uint16_t* __restrict__ g, int64_t ld, int row0, int r
 }
 
 // M/N-contiguous operand: k rows [k0, k0+BK) x cols [col0, col0+R) -> slot [BK][R]
-template <int R, int NW, int BK = 32, bool BUF = false, int POL = 0>
+template <int R, int NW, int BK = 32, bool BUF = false>
 PZ_DEV void stage_mn(const uint16_t* __restrict__ g, int64_t ld, int col0, int cols_valid, int k0,
                      PZ_LDS char* tile, int wave, int lane, i32x4_t rs = {}) {
   constexpr int ROW_BYTES = R * 2;
@@ -205,7 +189,7 @@ PZ_DEV void stage_mn(const uint16_t* __restrict__ g, int64_t ld, int col0, int c
     gc = gc < cols_valid ? gc : cols_valid - 8;
     if constexpr (BUF) {
       const uint32_t voff = (static_cast<uint32_t>(kr) * static_cast<uint32_t>(ld) + gc) * 2u;
-      blds16<POL>(rs, voff, __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(k0) * static_cast<uint32_t>(ld) * 2u),
+      blds16<0>(rs, voff, __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(k0) * static_cast<uint32_t>(ld) * 2u),
              lds_addr(tile + kbase * ROW_BYTES));
     } else {
       const uint16_t* src = g + static_cast<int64_t>(k0 + kr) * ld + gc;
@@ -217,17 +201,6 @@ PZ_DEV void stage_mn(const uint16_t* __restrict__ g, int64_t ld, int col0, int c
 template <int N>
 PZ_DEV void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
-// as wait_newer, with ONE extra (prefetch) operation issued after each step's G stage DMAs
-template <int G, int MAXN>
-PZ_DEV void wait_newer_pf(int n) {
-  if constexpr (MAXN == 0) {
-    wait_vm<1>();
-  } else {
-    if (n >= MAXN) wait_vm<MAXN * G + 1>();
-    else wait_newer_pf<G, MAXN - 1>(n);
-  }
 }
 
 // wait until at most n (<= MAXN) younger ring steps of G LDS-DMA instructions each are in flight

@@ -15,16 +15,22 @@
 //    ds_read_b64_tr_b16 — no transpose kernels, no second weight copy.
 //  * global->LDS by global_load_lds_dwordx4 (LDS-DMA, 1 KiB per wave-instruction; swizzle on the
 //    per-lane SOURCE address + the read, rule 21).
-//  * Pipeline: a ring of NS = 4 LDS slots, each one 32-deep K step. Loads run NS-1 steps
-//    ahead; each step waits with a COUNTED `s_waitcnt vmcnt((NS-2)G)` (G = LDS-DMA instructions per
-//    wave per step) so the NS-2 younger steps stay in flight across the raw `s_barrier` — never a
-//    vmcnt(0) drain in the loop (guide "Pipelining across barriers", T3/T4). One barrier per step
-//    covers both hazards: RAW (every wave's DMA for slot t landed) and WAR (every wave's reads of
-//    slot t-1, which the step re-fills, completed: lgkmcnt(0) before the barrier).
+//  * Pipeline: a ring of NS LDS slots, each one 32- or 64-deep K step (the table below). On the
+//    32-deep rings loads run NS-1 steps ahead; each step waits with a COUNTED
+//    `s_waitcnt vmcnt((NS-2)G)` (G = LDS-DMA instructions per wave per step) so the NS-2 younger
+//    steps stay in flight across the raw `s_barrier` — never a vmcnt(0) drain in the loop (guide
+//    "Pipelining across barriers", T3/T4). One barrier per step covers both hazards: RAW (every
+//    wave's DMA for slot t landed) and WAR (every wave's reads of slot t-1, which the step
+//    re-fills, completed: lgkmcnt(0) before the barrier). The 64-deep 2-slot ring (the default
+//    for bf16) is described above its loop in gemm_body.
 //  * MFMA clusters bracketed by s_setprio(1)/(0) (T5).
 //  * XCD-aware bijective block remap (T1) + grouped tile order for L2 reuse.
-//  * Tile configs 256x256 (8 waves), 256x128 (8 waves), 128x128 (4 waves, 2 blocks/CU), chosen
-//    per shape so the grid covers the 256 CUs.
+//  * Tile configs 256x256 (8 waves), 256x128 (8 waves, or 4 waves with 2 blocks/CU), 128x128
+//    (4 waves, 2 blocks/CU), chosen per shape so the grid covers the 256 CUs.
+//  * The main loop comes in the numbered variants of the table below (template VAR; the number
+//    is what gemm_last reports). VAR 40 / 43, the 4-wave schedule, are in gemm_w4.h. VAR numbers
+//    in profiles/ that have no row in the table are deleted experiments: their code is in the
+//    history up to commit a839ea0.
 #include <cstdlib>
 #include <type_traits>
 
@@ -34,35 +40,77 @@
 namespace pz {
 namespace {
 
-constexpr int kBK = 32;  // K depth of one ring slot (BK64 variants: two of these per slot)
+constexpr int kBK = 32;  // K depth of one MFMA K block (a 64-deep ring slot holds two)
 
 #include "gemm_common.h"  // LDS-DMA, swizzles, fragment reads, tile order (shared with gemm_sk.hip)
 
-// Main-loop variants (template VAR). The library instantiates 0 (flat DMA, ragged > 4 GiB
-// operands), 6 (buffer DMA, 32-deep ring), 30 (buffer DMA, 64-deep 2-slot ring, the default),
-// 8 / 9 (fp8 e4m3 / e5m2 x e4m3), 10 / 11 (their buffer-DMA forms, PZ_GEMM_F8BUF=1) and 12 / 13
-// (fp8 on the 64-deep buffer-DMA ring: 128 K-bytes per slot, two MFMA K-steps). The
-// rest are tools/gemm_lab probes whose measurements are in profiles/: 1 / 2 / 3 (no MFMA / no
-// DMA / no fragment reads), 4 (no deferred wait), 5 / 23 (3- / 5-slot rings), 20 / 21 / 31
-// (64-deep ring with flat DMA / split staging), 24 (L2 prefetch), 25 (buffer DMA for M/N-
-// contiguous operands only), 27-29 (cache policies), 41 (32x32x16 MFMA).
-// Per-variant ring geometry: VAR 20/21/30/31 stage 64-deep K steps into two 64 KiB slots (one
-// MFMA interval = 64 MFMAs per wave, half the barriers per FLOP of the 32-deep ring)
-template <int VAR> constexpr int var_bk() {
-  return (VAR == 20 || VAR == 21 || VAR == 30 || VAR == 31 || VAR == 32 || VAR == 33 || VAR == 12 || VAR == 13) ? 64 : 32;
-}
-template <int VAR> constexpr int var_ns() {
-  return (VAR == 5 || VAR == 7 || VAR == 16 || VAR == 17) ? 3 : VAR == 23 ? 5 : (var_bk<VAR>() == 64 ? 2 : 4);
-}
-// VAR 7: buffer DMA on a 3-slot 32-deep ring, for 4-wave 256x128 tiles that run TWO workgroups
-// per CU (72 KiB of LDS and <= 256 VGPRs each): one workgroup's epilogue overlaps the other's
-// main loop (the hardware interleaves the two instead of a barrier-phased ping-pong)
-// VAR 16 / 17: the fp8 forward (VAR 15) / e5m2 x e4m3 dX (VAR 9) the same way — 4-wave 256x128
-// tiles, 3-slot ring (72 KiB), two workgroups per CU: at K = 1024 an fp8 tile's epilogue (the
-// stage math, the e4m3 / e5m2 copies, the bitmask) costs about what its main loop does, and the
-// other workgroup's MFMAs run through it
-template <int VAR> constexpr int var_waves_per_eu() { return (VAR == 7 || VAR == 16 || VAR == 17) ? 2 : 1; }
+// fp8 operand forms: what the bytes of A and B look like in memory
+enum F8Form {
+  F8_NONE,   // bf16 operands
+  F8_KC_KC,  // both K-contiguous ([M][K] x [N][K] bytes)
+  F8_KC_MN,  // A K-contiguous, B [K][N] (the e4m3 weights in their natural [in, out] layout)
+  F8_MN_MN,  // A [K][M] e4m3, B [K][N] e5m2 (the weight gradient; K = batch rows)
+};
 
+// One row per main-loop variant: everything gemm_body does differently for a VAR number.
+struct Variant {
+  int var;           // the template key and what gemm_last reports
+  int bk;            // K depth of a ring slot in 16-bit units (fp8: twice as many K bytes)
+  int ns;            // ring slots
+  int waves_per_eu;  // 2: 4-wave workgroups sized so that two share a CU
+  bool buf;          // stage_kc / stage_mn address through a buffer descriptor, not flat pointers
+  bool full_kc;      // K-contiguous operands are staged as full row tiles, without a row clamp
+  F8Form f8;
+  bool a_e5m2;       // fp8: A holds e5m2 gradients (the backward dX GEMM, EPI_BWD epilogues)
+};
+
+// LDS-DMA addressing, measured (tools/gemm_lab, same box): buffer is +6..10% on the M/N-contiguous
+// operands, whose k-row addresses otherwise cost 64-bit multiplies every step, and 1.5..5% slower
+// on K-contiguous ones (measured, not kept: VAR 25 = buffer for M/N-contiguous only). The
+// M/N-contiguous fp8 operands (stage_mn8) are always buffer-addressed, whatever `buf` says.
+constexpr Variant kVariants[] = {
+    // {var, bk, ns, waves_per_eu, buf, full_kc, f8, a_e5m2}
+    // 0: flat DMA on the 4-slot 32-deep ring: operands that reach past 4 GiB from their base
+    {0, 32, 4, 1, false, false, F8_NONE, false},
+    // 6: buffer DMA on the 4-slot 32-deep ring: what 30 does not take (ragged tiles, K % 64,
+    // 128x128 tiles)
+    {6, 32, 4, 1, true, false, F8_NONE, false},
+    // 7: buffer DMA on a 3-slot 32-deep ring, for 4-wave 256x128 tiles that run TWO workgroups
+    // per CU (72 KiB of LDS and <= 256 VGPRs each): one workgroup's epilogue overlaps the other's
+    // main loop (the hardware interleaves the two instead of a barrier-phased ping-pong).
+    // Measured by tools/gemm_stamps, not dispatched for bf16
+    {7, 32, 3, 2, true, false, F8_NONE, false},
+    // 8: e4m3 x e4m3, both K-contiguous, v_mfma_scale_f32_32x32x64_f8f6f4 with unit block scales:
+    // a ring slot holds 64 K-bytes per row (the bf16 slot geometry), one MFMA K-step
+    {8, 32, 4, 1, false, false, F8_KC_KC, false},
+    // 9: A in e5m2 (bf8: gradients, wide range), B in e4m3 — the backward dX GEMM dZ8 · W8ᵀ of
+    // the fp8 policy, with the backward (EPI_BWD) epilogues
+    {9, 32, 4, 1, false, false, F8_KC_KC, true},
+    // 14: the fp8 weight-gradient GEMM dW = X8ᵀ · dZ8 — e4m3 activations (A) x e5m2 output
+    // gradients (B), BOTH M/N-contiguous, staged as k-row images and read with the transposing
+    // ds_read_b64_tr_b8 (no transposed copies), bf16 output
+    {14, 32, 4, 1, false, false, F8_MN_MN, false},
+    // 15: the fp8 forward X8 · W8 with the e4m3 weights in their natural [in, out] layout (B
+    // N-contiguous, transposing 8-bit reads) — the same copy the backward dX GEMM reads as its
+    // K-contiguous B, so one e4m3 weight copy serves both and no transposed copy is made
+    {15, 32, 4, 1, false, false, F8_KC_MN, false},
+    // 16 / 17: the fp8 forward (15) / e5m2 x e4m3 dX (9) the way of 7 — 4-wave 256x128 tiles,
+    // 3-slot ring (72 KiB), two workgroups per CU: at K = 1024 an fp8 tile's epilogue (the stage
+    // math, the e4m3 / e5m2 copies, the bitmask) costs about what its main loop does, and the
+    // other workgroup's MFMAs run through it
+    {16, 32, 3, 2, false, false, F8_KC_MN, false},
+    {17, 32, 3, 2, false, false, F8_KC_KC, true},
+    // 30: buffer DMA on a 2-slot 64-deep ring (two 64 KiB slots: one MFMA interval = 64 MFMAs per
+    // wave, half the barriers per FLOP of the 32-deep ring), the bf16 default. Full row tiles of
+    // the K-contiguous operands only (use_bk64 checks M % BM, N % BN)
+    {30, 64, 2, 1, true, true, F8_NONE, false},
+};
+
+constexpr Variant variant(int var) {
+  for (const Variant& v : kVariants)
+    if (v.var == var) return v;
+  return {-1, 32, 4, 1, false, false, F8_NONE, false};  // no row: gemm_body refuses to compile
+}
 
 template <int BM, int BN, int WM, int WN, int NS_ = 4, int BK_ = 32>
 struct Cfg {
@@ -80,13 +128,14 @@ struct Cfg {
   static constexpr int A_BYTES = BM * BK * 2;
   static constexpr int B_BYTES = BN * BK * 2;
   static constexpr int SLOT_BYTES = A_BYTES + B_BYTES;
-  static constexpr int LDS_BYTES = NS * SLOT_BYTES + 256;  // + L2-prefetch sink (VAR 24)
+  static constexpr int LDS_BYTES = NS * SLOT_BYTES;  // the epilogues' BM x BN bf16 C image fits the ring
   static constexpr int GA = A_BYTES / 1024 / NW;  // LDS-DMA instructions per wave per slot
   static constexpr int GB = B_BYTES / 1024 / NW;
   static constexpr int G = GA + GB;
   static_assert(TM >= 1 && TN >= 1, "wave tile must hold at least one 16x16 MFMA tile");
   static_assert(GA >= 1 && GB >= 1 && GA * 1024 * NW == A_BYTES && GB * 1024 * NW == B_BYTES, "stage split");
-  static_assert(LDS_BYTES <= 160 * 1024 + 256, "LDS budget");
+  static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
+  static_assert(BM * BN * 2 <= LDS_BYTES, "epilogue_lds keeps the tile's bf16 C image in the ring");
 };
 
 
@@ -240,9 +289,11 @@ template <int BM, int BN, int WM, int WN, bool A_KC, bool B_KC, typename OutT, t
 PZ_DEV void gemm_body(const GemmArgs& p, int wgid) {
   static_assert(EK == EK_ANY || std::is_same<OutT, uint16_t>::value, "specialised epilogues: bf16 output");
   PZ_STAMP(0);
-  constexpr int BK = var_bk<VAR>();
+  constexpr Variant V = variant(VAR);
+  static_assert(V.var == VAR, "this VAR has no row in kVariants: a deleted experiment (see the header comment)?");
+  constexpr int BK = V.bk;
   constexpr int KB = BK / 32;  // 32-deep MFMA K blocks per ring slot
-  using C = Cfg<BM, BN, WM, WN, var_ns<VAR>(), BK>;
+  using C = Cfg<BM, BN, WM, WN, V.ns, BK>;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   PZ_LDS char* smem = (PZ_LDS char*)(smem_raw);
 
@@ -259,39 +310,22 @@ PZ_DEV void gemm_body(const GemmArgs& p, int wgid) {
   const uint16_t* __restrict__ A = static_cast<const uint16_t*>(p.A);
   const uint16_t* __restrict__ B = static_cast<const uint16_t*>(p.B);
 
-  // VAR 8: e4m3 operands (both K-contiguous), v_mfma_scale_f32_32x32x64_f8f6f4 with unit block
-  // scales: a ring slot holds 64 K-bytes per row (the bf16 slot geometry), one MFMA K-step
-  // VAR 9: A in e5m2 (bf8: gradients, wide range), B in e4m3 — the backward dX GEMM
-  // dZ8 · W8ᵀ of the fp8 policy, with the backward (EPI_BWD) epilogues
-  // VAR 10 / 11: VAR 8 / 9 with buffer-addressed staging DMA
-  // VAR 14: the fp8 weight-gradient GEMM dW = X8ᵀ · dZ8 — e4m3 activations (A) x e5m2 output
-  // gradients (B), BOTH M/N-contiguous ([K][M] / [K][N] bytes, K = batch rows), staged as k-row
-  // images and read with the transposing ds_read_b64_tr_b8 (no transposed copies), bf16 output
-  constexpr bool F8_MN = VAR == 14;
-  // VAR 15: the fp8 forward X8 · W8 with the e4m3 weights in their natural [in, out] layout
-  // (B N-contiguous, transposing 8-bit reads) — the same copy the backward dX GEMM reads as its
-  // K-contiguous B, so one e4m3 weight copy serves both and no transposed copy is made
-  constexpr bool F8_MNB = VAR == 15 || VAR == 16;
-  constexpr bool F8 = VAR == 8 || VAR == 9 || VAR == 10 || VAR == 11 || VAR == 12 || VAR == 13 || VAR == 17 || F8_MN ||
-                      F8_MNB;
-  constexpr bool F8_BWD = VAR == 9 || VAR == 11 || VAR == 13 || VAR == 17;
-  constexpr int F8_FMT_A = F8_BWD ? 1 : 0;  // MFMA format codes: 0 = fp8 e4m3, 1 = bf8 e5m2
+  constexpr bool F8_MN = V.f8 == F8_MN_MN;
+  constexpr bool F8_MNB = V.f8 == F8_KC_MN;
+  constexpr bool F8 = V.f8 != F8_NONE;  // 32x32 accumulator tiles
+  constexpr int F8_FMT_A = V.a_e5m2 ? 1 : 0;  // MFMA format codes: 0 = fp8 e4m3, 1 = bf8 e5m2
   constexpr int F8_FMT_B = F8_MN ? 1 : 0;
   static_assert(!F8 || ((F8_MN ? (!A_KC && !B_KC) : F8_MNB ? (A_KC && !B_KC) : (A_KC && B_KC)) &&
                          std::is_same<OutT, uint16_t>::value),
-                "fp8: K-contiguous in (M/N-contiguous for VAR 14), bf16 out");
-  // VAR 41 (lab A/B): bf16 on v_mfma_f32_32x32x16_bf16 (32x32 accumulator tiles, the fp8 layout)
-  constexpr bool M32 = VAR == 41;
-  static_assert(!M32 || (A_KC && B_KC && std::is_same<OutT, uint16_t>::value), "M32: K-contiguous in, bf16 out");
-  constexpr bool ACC32 = F8 || M32;  // 32x32 accumulator tiles
+                "fp8: the operand layouts of the variant's F8Form, bf16 out");
+  // (measured, not kept: bf16 on v_mfma_f32_32x32x16_bf16, VAR 41, profiles/r2_ab_mfma_32x32_vs_16x16.txt)
   constexpr int TM8 = C::WTM / 32, TN8 = C::WTN / 32;
   struct Frags16 { i16x8_t a[KB][C::TM]; i16x8_t b[KB][C::TN]; };
   struct Frags8 { i32x8_t a[KB][TM8]; i32x8_t b[KB][TN8]; };  // KB MFMA K-steps of 64 bytes
-  struct Frags32 { i16x8_t a[2][TM8]; i16x8_t b[2][TN8]; };
-  using Frags = std::conditional_t<F8, Frags8, std::conditional_t<M32, Frags32, Frags16>>;
-  using AccT = std::conditional_t<ACC32, f32x16_t[TM8][TN8], f32x4_t[C::TM][C::TN]>;
+  using Frags = std::conditional_t<F8, Frags8, Frags16>;
+  using AccT = std::conditional_t<F8, f32x16_t[TM8][TN8], f32x4_t[C::TM][C::TN]>;
   AccT acc;
-  if constexpr (ACC32) {
+  if constexpr (F8) {
 #pragma unroll
     for (int i = 0; i < TM8; ++i)
 #pragma unroll
@@ -303,22 +337,13 @@ PZ_DEV void gemm_body(const GemmArgs& p, int wgid) {
       for (int j = 0; j < C::TN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   }
 
-  // VAR 33 (lab A/B): VAR 30 without the s_setprio bracket around the MFMA block; GemmArgs::prio = 0
-  // (PZ_GEMM_PRIO=0) drops it at run time (a uniform scalar branch per MFMA block)
-  constexpr bool PRIO = VAR != 33;
-  const bool prio = PRIO && p.prio != 0;
+  // GemmArgs::prio = 0 (PZ_GEMM_PRIO=0) drops the s_setprio bracket around the MFMA block at run
+  // time (a uniform scalar branch per MFMA block). (measured, not kept: compiled out, VAR 33 —
+  // profiles/r4_ab_session.txt: its apparent gain came from run order)
+  const bool prio = p.prio != 0;
   auto mfma_step = [&](const Frags& f) {
     if (prio) __builtin_amdgcn_s_setprio(1);
-    if constexpr (M32) {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int i = 0; i < TM8; ++i)
-#pragma unroll
-          for (int j = 0; j < TN8; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, f.b[ks][j]),
-                                                                __builtin_bit_cast(bf16x8_t, f.a[ks][i]), acc[i][j], 0, 0, 0);
-    } else if constexpr (F8) {
+    if constexpr (F8) {
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
@@ -343,15 +368,7 @@ PZ_DEV void gemm_body(const GemmArgs& p, int wgid) {
   auto read_frags = [&](int slot, Frags& f) {
     const PZ_LDS char* ta = smem + slot * C::SLOT_BYTES;
     const PZ_LDS char* tb = ta + C::A_BYTES;
-    if constexpr (M32) {  // lane l: row l&31, k [8*(l>>5) + 16*ks, +8) = 16-B chunk (l>>5) + 2ks
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-        for (int j = 0; j < TN8; ++j) f.b[ks][j] = frag_kc(tb, wn * C::WTN + j * 32 + (lane & 31), (lane >> 5) + 2 * ks);
-#pragma unroll
-        for (int i = 0; i < TM8; ++i) f.a[ks][i] = frag_kc(ta, wm * C::WTM + i * 32 + (lane & 31), (lane >> 5) + 2 * ks);
-      }
-    } else if constexpr (F8_MNB) {  // A: 16-B chunks of K-contiguous rows; B: transposing 8-bit reads
+    if constexpr (F8_MNB) {  // A: 16-B chunks of K-contiguous rows; B: transposing 8-bit reads
       const int h2 = 2 * (lane >> 5);
 #pragma unroll
       for (int j = 0; j < TN8; ++j) f.b[0][j] = frag_mn8<BN>(tb, wn * C::WTN + j * 32, lane);
@@ -405,94 +422,56 @@ PZ_DEV void gemm_body(const GemmArgs& p, int wgid) {
 
   const int nk = p.K / (F8 ? 2 * BK : BK) / split;  // K steps of this slice (fp8: 2 bytes per 16-bit unit)
   const int kt0 = slice * nk;
-  // LDS-DMA addressing per operand: buffer (MUBUF, 32-bit per-lane offsets from one descriptor)
-  // or flat (64-bit pointers). Measured (tools/gemm_lab, same box): buffer is +6..10% on the
-  // M/N-contiguous operands, whose k-row addresses otherwise cost 64-bit multiplies every step,
-  // and 1.5..5% slower on K-contiguous ones (VAR 25 = buffer for M/N-contiguous only)
-  constexpr bool BUF_A = VAR == 6 || VAR == 7 || (VAR >= 10 && VAR <= 13) || VAR == 41 || (VAR == 25 && !A_KC) || (VAR >= 27 && VAR <= 33);
-  constexpr bool BUF_B = VAR == 6 || VAR == 7 || (VAR >= 10 && VAR <= 13) || VAR == 41 || (VAR == 25 && !B_KC) || (VAR >= 27 && VAR <= 33);
-  constexpr int POL = VAR >= 27 && VAR <= 29 ? VAR - 26 : 0;
-  // VAR 30/31: full row tiles of the K-contiguous operands (use_bk64 checks M % BM, N % BN)
-  constexpr bool FULL_KC = VAR == 30 || VAR == 31 || VAR == 32 || VAR == 33 || VAR == 12 || VAR == 13;
   const i32x4_t rs_a = buf_rsrc(A), rs_b = buf_rsrc(B);
   // staging works in 16-bit units: an e4m3 row of 64 K-bytes is the same 64-B piece
   const int64_t lda = F8 ? p.lda / 2 : p.lda, ldb = F8 ? p.ldb / 2 : p.ldb;
   // (measured, not kept: DMA issued by waves 0-3 only, twice the instructions each: -2..4%)
   constexpr int NWD = C::NW;
-  constexpr bool PF = VAR == 24;      // L2 prefetch kPfAhead steps beyond the staged one
-  constexpr int kPfAhead = 3;
-  constexpr int GD = C::G + (PF ? 1 : 0);
   // TEAM waves (team-local index tw) issue one operand's DMA of a step
   auto stage_a_t = [&](int kt, auto team, int tw) {
     constexpr int TEAM = decltype(team)::value;
     PZ_LDS char* base = smem + (kt % C::NS) * C::SLOT_BYTES;
     if constexpr (F8_MN) stage_mn8<BM, TEAM, 64>(lda, m0, (kt0 + kt) * 64, base, tw, lane, rs_a);
-    else if constexpr (A_KC) stage_kc<BM, TEAM, BK, BUF_A, POL, FULL_KC>(A, lda, m0, p.M, (kt0 + kt) * BK, base, tw, lane, rs_a);
-    else stage_mn<BM, TEAM, BK, BUF_A, POL>(A, lda, m0, p.M, (kt0 + kt) * BK, base, tw, lane, rs_a);
+    else if constexpr (A_KC) stage_kc<BM, TEAM, BK, V.buf, V.full_kc>(A, lda, m0, p.M, (kt0 + kt) * BK, base, tw, lane, rs_a);
+    else stage_mn<BM, TEAM, BK, V.buf>(A, lda, m0, p.M, (kt0 + kt) * BK, base, tw, lane, rs_a);
   };
   auto stage_b_t = [&](int kt, auto team, int tw) {
     constexpr int TEAM = decltype(team)::value;
     PZ_LDS char* base = smem + (kt % C::NS) * C::SLOT_BYTES + C::A_BYTES;
     if constexpr (F8_MN || F8_MNB) stage_mn8<BN, TEAM, 64>(ldb, n0, (kt0 + kt) * 64, base, tw, lane, rs_b);
-    else if constexpr (B_KC) stage_kc<BN, TEAM, BK, BUF_B, POL, FULL_KC>(B, ldb, n0, p.N, (kt0 + kt) * BK, base, tw, lane, rs_b);
-    else stage_mn<BN, TEAM, BK, BUF_B, POL>(B, ldb, n0, p.N, (kt0 + kt) * BK, base, tw, lane, rs_b);
+    else if constexpr (B_KC) stage_kc<BN, TEAM, BK, V.buf, V.full_kc>(B, ldb, n0, p.N, (kt0 + kt) * BK, base, tw, lane, rs_b);
+    else stage_mn<BN, TEAM, BK, V.buf>(B, ldb, n0, p.N, (kt0 + kt) * BK, base, tw, lane, rs_b);
   };
   auto stage_a = [&](int kt) { stage_a_t(kt, std::integral_constant<int, NWD>{}, wave); };
   auto stage_b = [&](int kt) { stage_b_t(kt, std::integral_constant<int, NWD>{}, wave); };
-  auto prefetch = [&](int kt) {  // one dword per 128-B line of step kt's A and B tiles
-    kt = min(kt, nk - 1);
-    const int k0 = (kt0 + kt) * BK;
-    uint32_t sink = lds_addr(smem + C::NS * C::SLOT_BYTES);
-    const int tid = wave * 64 + lane;  // 512 lanes: A lines first, then B lines
-    auto line = [&](const uint16_t* g, int64_t ld, bool kc, int R, int r0, int valid, int idx) -> const void* {
-      if (kc) {  // idx = row
-        int gr = min(r0 + idx, valid - 1);
-        return g + static_cast<int64_t>(gr) * ld + k0;
-      }
-      const int per = (R * 2) / 128;  // lines per k row
-      const int kr = idx / per, c = (idx % per) * 64;
-      return g + static_cast<int64_t>(k0 + kr) * ld + min(r0 + c, valid - 8);
-    };
-    const int na = A_KC ? BM : BK * (BM * 2 / 128);
-    const int nb = B_KC ? BN : BK * (BN * 2 / 128);
-    if (tid < na) glds4(line(A, lda, A_KC, BM, m0, p.M, tid), sink);
-    else if (tid < na + nb) glds4(line(B, ldb, B_KC, BN, n0, p.N, tid - na), sink);
-    else glds4(A, sink);
-  };
-  auto stage = [&](int kt, int slot) {  // slot == kt % NS
-    (void)slot;
+  auto stage = [&](int kt) {
     stage_a(kt);
     stage_b(kt);
-    if constexpr (PF) prefetch(kt + kPfAhead);
   };
 
   constexpr int NS = C::NS;
   // Measured, not kept: staging K-contiguous operands in PAIRS of steps so both 64-B halves of
   // every 128-B line are requested back to back (halved L1->L2 requests, matched hipBLASLt's
-  // request count) ran 2-4% SLOWER than the plain ring with DEFER below.
-  constexpr bool DEFER = VAR != 4;  // group 0 waits for step t+1 at the END of M_t (+2..6%)
+  // request count) ran 2-4% SLOWER than the plain ring.
   if constexpr (BK == 64) {
-    // Ping-pong over 64-deep steps in a 2-slot ring (VAR 20: waves 0-3 issue every DMA in their
-    // read interval; VAR 21: waves 0-3 stage A in their read interval R_t while waves 4-7 stage
-    // B of the same step t+1 at the head of their MFMA interval M_{t-1} — the same barrier
-    // interval). Interval 2t: G0 R_t | G1 M_{t-1}; interval 2t+1: G0 M_t | G1 R_t. Slot (t+1)%2
-    // was last read by G1 in interval 2t-1, so step t+1 is issued in interval 2t and awaited
-    // (vmcnt(0)) at the end of interval 2t+1 by every wave, before G0 reads it in 2t+2.
+    // Ping-pong over 64-deep steps in a 2-slot ring: waves 0-3 (G0) issue every DMA of step t+1
+    // in their read interval R_t. Interval 2t: G0 R_t | G1 M_{t-1}; interval 2t+1: G0 M_t | G1 R_t.
+    // Slot (t+1)%2 was last read by G1 in interval 2t-1, so step t+1 is issued in interval 2t and
+    // awaited (vmcnt(0)) at the end of interval 2t+1 by every wave, before G0 reads it in 2t+2.
+    // (measured, not kept: waves 4-7 staging B at the head of their MFMA interval, VAR 31,
+    // profiles/r5_ab_split_staging.txt)
     static_assert(C::NW == 8, "BK64 ping-pong needs 8 waves");
     const int grp = wave >> 2, tw = wave & 3;
     using T4 = std::integral_constant<int, 4>;
     auto stage_g0 = [&](int kt) {
       stage_a_t(kt, T4{}, tw);
-      if constexpr (!(VAR == 21 || VAR == 31)) stage_b_t(kt, T4{}, tw);  // 21 / 31: group 1 stages B
+      stage_b_t(kt, T4{}, tw);
     };
-    stage(0, 0);
+    stage(0);
     wait_vm<0>();
     barrier();
     PZ_STAMP(1);
-    if (grp == 1) {
-      if ((VAR == 21 || VAR == 31) && nk > 1) stage_b_t(1, T4{}, tw);
-      barrier();
-    }
+    if (grp == 1) barrier();
     for (int t = 0; t < nk; ++t) {
       if (grp == 0 && t + 1 < nk) stage_g0(t + 1);
       Frags f;
@@ -500,7 +479,6 @@ PZ_DEV void gemm_body(const GemmArgs& p, int wgid) {
       if (grp == 1) wait_vm<0>();  // step t+1 (issued in M_{t-1}) landed before interval 2t+2
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       barrier();
-      if ((VAR == 21 || VAR == 31) && grp == 1 && t + 2 < nk) stage_b_t(t + 2, T4{}, tw);
       mfma_step(f);
       if (grp == 0) wait_vm<0>();
       barrier();
@@ -510,7 +488,7 @@ PZ_DEV void gemm_body(const GemmArgs& p, int wgid) {
   } else {
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s)
-    if (s < nk) stage(s, s);
+    if (s < nk) stage(s);
 
   if constexpr (C::NW == 8) {
     // Ping-pong (8 waves = 2 per SIMD). Waves 0-3 and 4-7 sit on the same four SIMDs and run one
@@ -519,45 +497,29 @@ PZ_DEV void gemm_body(const GemmArgs& p, int wgid) {
     // step t: R_t = {stage t+NS-1, [group 1: wait until step t+1 landed], read slot t,
     // lgkmcnt(0)} | barrier | M_t = {MFMAs, [group 0: wait until step t+1 landed]} | barrier.
     // Group 0 runs one interval AHEAD, so its wait can sit at the end of its MFMA block (one
-    // interval more of DMA latency hidden) and still precede the barrier that opens R_{t+1} for
-    // both groups. Hazards: slot t+1 is waited for by every wave before that barrier; slot
-    // (t+NS-1)%NS = (t-1)%NS was last read in R_{t-1} and every wave retired those reads
+    // interval more of DMA latency hidden: +2..6%) and still precede the barrier that opens
+    // R_{t+1} for both groups. Hazards: slot t+1 is waited for by every wave before that barrier;
+    // slot (t+NS-1)%NS = (t-1)%NS was last read in R_{t-1} and every wave retired those reads
     // (lgkmcnt(0)) before the barrier that precedes R_t of either group.
     const int grp = wave >> 2;
-    auto wait_step = [&](int n) {
-      if constexpr (PF) wait_newer_pf<GD, NS - 2>(n);
-      else wait_newer<GD, NS - 2>(n);
-    };
+    auto wait_step = [&](int n) { wait_newer<C::G, NS - 2>(n); };
     wait_step(min(nk, NS - 1) - 1);  // step 0 landed
     barrier();
     PZ_STAMP(1);
     if (grp == 1) barrier();
     for (int t = 0; t < nk; ++t) {
-      if (VAR != 2 && t + NS - 1 < nk) stage(t + NS - 1, (t + NS - 1) % NS);
-      if (!DEFER || grp == 1) wait_step(min(nk - 1, t + NS - 1) - (t + 1));  // step t+1 landed
+      if (t + NS - 1 < nk) stage(t + NS - 1);
+      if (grp == 1) wait_step(min(nk - 1, t + NS - 1) - (t + 1));  // step t+1 landed
       Frags f;
-      if constexpr (VAR == 3) {  // perf probe: no fragment reads
-#pragma unroll
-        for (int i = 0; i < C::TM; ++i) f.a[0][i] = i16x8_t{(short)i, 1, 2, 3, 4, 5, 6, (short)t};
-#pragma unroll
-        for (int j = 0; j < C::TN; ++j) f.b[0][j] = i16x8_t{(short)j, 1, 2, 3, 4, 5, 6, (short)t};
-      } else {
-        read_frags(t % NS, f);
-      }
+      read_frags(t % NS, f);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       barrier();
-      if constexpr (VAR != 1) {
-        mfma_step(f);
-      } else {  // perf probe: no MFMAs (keep the fragments live)
-#pragma unroll
-        for (int i = 0; i < C::TM; ++i) acc[i][0][0] += static_cast<float>(f.a[0][i][0] + f.b[0][i % C::TN][1]);
-      }
-      if (DEFER && grp == 0) wait_step(min(nk - 1, t + NS - 1) - (t + 1));
+      mfma_step(f);
+      if (grp == 0) wait_step(min(nk - 1, t + NS - 1) - (t + 1));
       barrier();
     }
     if (grp == 0) barrier();
     PZ_STAMP(2);
-    if constexpr (PF) wait_vm<0>();  // no prefetch DMA may outlive the workgroup's LDS
   } else {
   PZ_STAMP(1);  // (4-wave tiles: before the first wait)
   for (int t = 0; t < nk; ++t) {
@@ -565,7 +527,7 @@ PZ_DEV void gemm_body(const GemmArgs& p, int wgid) {
     wait_newer<C::G, NS - 2>(min(nk - 1, t + NS - 2) - t);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if (t + NS - 1 < nk) stage(t + NS - 1, (t + NS - 1) % NS);
+    if (t + NS - 1 < nk) stage(t + NS - 1);
     Frags f;
     read_frags(t % NS, f);
     mfma_step(f);
@@ -583,11 +545,11 @@ PZ_DEV void gemm_body(const GemmArgs& p, int wgid) {
   // XCD cost ~2.7x the publish, measured 19-23 us of a split-K GEMM's 85-95 us) and no acquire.
   // (measured, not kept: plain stores + agent release / acquire fences, VAR 32)
   if (split > 1) {
-    constexpr int CH = ACC32 ? TM8 * TN8 * 4 : C::TM * C::TN;  // f32x4 chunks per lane
+    constexpr int CH = F8 ? TM8 * TN8 * 4 : C::TM * C::TN;  // f32x4 chunks per lane
     const int tid = threadIdx.x;
     auto get_chunk = [&](auto cc) -> f32x4_t {
       constexpr int c = decltype(cc)::value;
-      if constexpr (ACC32) {
+      if constexpr (F8) {
         constexpr int i = (c / 4) / TN8, j = (c / 4) % TN8, q = 4 * (c % 4);
         return f32x4_t{acc[i][j][q], acc[i][j][q + 1], acc[i][j][q + 2], acc[i][j][q + 3]};
       } else {
@@ -629,7 +591,7 @@ PZ_DEV void gemm_body(const GemmArgs& p, int wgid) {
         f32x4_t v = get_chunk(std::integral_constant<int, c>{}) + ld(mate, c);
         if (split >= 4) v = v + (ld(pair2, c) + ld(pair2 + 1, c));
         if (split >= 8) v = v + ((ld(quad4, c) + ld(quad4 + 1, c)) + (ld(quad4 + 2, c) + ld(quad4 + 3, c)));
-        if constexpr (ACC32) {
+        if constexpr (F8) {
           constexpr int i = (c / 4) / TN8, j = (c / 4) % TN8, q = 4 * (c % 4);
           acc[i][j][q] = v[0]; acc[i][j][q + 1] = v[1]; acc[i][j][q + 2] = v[2]; acc[i][j][q + 3] = v[3];
         } else {
@@ -647,9 +609,9 @@ PZ_DEV void gemm_body(const GemmArgs& p, int wgid) {
   OutT* __restrict__ Cp = static_cast<OutT*>(p.C);
   const AuxT* __restrict__ aux = static_cast<const AuxT*>(p.aux);
   const int g4 = 4 * (lane >> 4);
-  if constexpr (ACC32) {
+  if constexpr (F8) {
     const float alpha = p.alpha * (p.scale_a != nullptr ? *p.scale_a : 1.f) * (p.scale_b != nullptr ? *p.scale_b : 1.f);
-    if constexpr (F8_BWD || M32) epilogue_lds<BM, BN, WM, WN, Lay32<TM8, TN8>, false, EK>(p, acc, smem, m0, n0, wm, wn, lane, alpha);
+    if constexpr (V.a_e5m2) epilogue_lds<BM, BN, WM, WN, Lay32<TM8, TN8>, false, EK>(p, acc, smem, m0, n0, wm, wn, lane, alpha);
     else epilogue_lds<BM, BN, WM, WN, Lay32<TM8, TN8>, true, EK>(p, acc, smem, m0, n0, wm, wn, lane, alpha);
   } else if constexpr (std::is_same<OutT, uint16_t>::value) {
     epilogue_lds<BM, BN, WM, WN, Lay16<C::TM, C::TN>, false, EK>(p, acc, smem, m0, n0, wm, wn, lane, p.alpha);
@@ -685,7 +647,7 @@ PZ_DEV void gemm_body(const GemmArgs& p, int wgid) {
 }
 
 template <int BM, int BN, int WM, int WN, bool A_KC, bool B_KC, typename OutT, typename AuxT, int VAR, int EK = EK_ANY>
-__global__ void __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(var_waves_per_eu<VAR>())))
+__global__ void __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(variant(VAR).waves_per_eu)))
 gemm_mfma_kernel(const GemmArgs p) {
   gemm_body<BM, BN, WM, WN, A_KC, B_KC, OutT, AuxT, VAR, EK>(p, xcd_remap(blockIdx.x, gridDim.x));
 }
@@ -703,7 +665,7 @@ struct GemmPairArgs {
 };
 
 template <int BM, int BN, int WM, int WN, bool A_KC, bool B_KC, typename OutT, typename AuxT, int VAR, int EK = EK_ANY>
-__global__ void __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(var_waves_per_eu<VAR>())))
+__global__ void __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(variant(VAR).waves_per_eu)))
 gemm_mfma_pair_kernel(const GemmPairArgs g) {
   const int w = xcd_remap(blockIdx.x, gridDim.x);
   const int second = w >= g.nwg0 ? 1 : 0;  // workgroup-uniform
@@ -712,7 +674,7 @@ gemm_mfma_pair_kernel(const GemmPairArgs g) {
 
 template <int BM, int BN, int WM, int WN, bool A_KC, bool B_KC, typename OutT, typename AuxT, int VAR, int EK = EK_ANY>
 hipError_t launch_cfg(const GemmArgs& p, hipStream_t s) {
-  using C = Cfg<BM, BN, WM, WN, var_ns<VAR>(), var_bk<VAR>()>;
+  using C = Cfg<BM, BN, WM, WN, variant(VAR).ns, variant(VAR).bk>;
   auto kern = gemm_mfma_kernel<BM, BN, WM, WN, A_KC, B_KC, OutT, AuxT, VAR, EK>;
   static bool attr_set = false;
   if (!attr_set) {
@@ -910,7 +872,7 @@ hipError_t launch_fp8(const GemmArgs& p, hipStream_t s) {
 
 template <typename OutT, int VAR, int EK>
 hipError_t launch_pair_cfg(const GemmPairArgs& g, int nwg, hipStream_t s) {
-  using C = Cfg<256, 256, 2, 4, var_ns<VAR>(), var_bk<VAR>()>;
+  using C = Cfg<256, 256, 2, 4, variant(VAR).ns, variant(VAR).bk>;
   auto kern = gemm_mfma_pair_kernel<256, 256, 2, 4, false, false, OutT, uint16_t, VAR, EK>;
   static bool attr_set = false;
   if (!attr_set) {

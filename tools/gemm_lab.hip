@@ -50,7 +50,7 @@ __global__ void ref_rows(const uint16_t* A, const uint16_t* B, float* R, int N, 
 }
 
 typedef hipError_t (*LaunchFn)(const GemmArgs&, hipStream_t);
-struct Variant {
+struct LabVariant {
   const char* name;
   LaunchFn fn;
   int split = 1;
@@ -68,9 +68,9 @@ struct Case {
   bool akc, bkc, f32out;
 };
 
-static std::vector<Variant> variants_for(const Case& c) {
+static std::vector<LabVariant> variants_for(const Case& c) {
   if (c.akc && !c.bkc && !c.f32out) {
-    std::vector<Variant> v = PZ_VARIANTS(true, false, uint16_t);
+    std::vector<LabVariant> v = PZ_VARIANTS(true, false, uint16_t);
     if (c.N <= 1024) {  // skinny forward (fwd_L3): split-K 2 (library) vs 256x128 tiles
       v.push_back({"bk64_s2", launch_cfg<256, 256, 2, 4, true, false, uint16_t, uint16_t, 30>, 2});
       v.push_back({"t256x128", launch_cfg<256, 128, 4, 2, true, false, uint16_t, uint16_t, 6>});
@@ -78,13 +78,9 @@ static std::vector<Variant> variants_for(const Case& c) {
     }
     return v;
   }
-  if (c.akc && c.bkc && !c.f32out) {
-    std::vector<Variant> v = PZ_VARIANTS(true, true, uint16_t);
-    v.push_back({"m32x32", launch_cfg<256, 256, 2, 4, true, true, uint16_t, uint16_t, 41>});
-    return v;
-  }
+  if (c.akc && c.bkc && !c.f32out) return PZ_VARIANTS(true, true, uint16_t);
   if (!c.akc && !c.bkc && c.f32out) {
-    std::vector<Variant> v = PZ_VARIANTS(false, false, float);
+    std::vector<LabVariant> v = PZ_VARIANTS(false, false, float);
     if (c.N <= 1024 || c.M <= 1024) {  // skinny dW: the library's split-K 4 plan (VAR 30)
       v.push_back({"bk64_s4", launch_cfg<256, 256, 2, 4, false, false, float, uint16_t, 30>, 4});
       v.push_back({"bk64_s2", launch_cfg<256, 256, 2, 4, false, false, float, uint16_t, 30>, 2});
