@@ -22,6 +22,7 @@
 #include <tuple>
 #include <vector>
 
+#include "gemm_dispatch.h"
 #include "json_format.h"
 #include "pz_kernels.h"
 
@@ -217,6 +218,25 @@ int* split_counters(int tiles, const c10::Device& dev) {
   return ptr;
 }
 
+// split-K: plan p for `split` K slices (1 = none): their fp32 slabs, which `ws` keeps alive (from
+// the caching allocator: stream-ordered reuse is safe), and the per-tile tickets
+void attach_split(pz::GemmArgs& p, int split, at::Tensor& ws, const Tensor& like) {
+  if (split <= 1) return;
+  ws = at::empty({pz::split_ws_floats(p, split)}, like.options().dtype(at::kFloat));
+  p.split_k = split;
+  p.ws = ws.data_ptr<float>();
+  p.counters = split_counters(pz::tiles(p, 256, 256), like.device());
+}
+
+// stream-K: the slabs and tickets of the one schedule of probs[0 .. n), on probs[0]
+void attach_sk(pz::GemmArgs* probs, int n, at::Tensor& ws, const Tensor& like) {
+  const int64_t sk_floats = pz::sk_ws_floats(probs, n);
+  if (sk_floats <= 0) return;
+  ws = at::empty({sk_floats}, like.options().dtype(at::kFloat));
+  probs[0].ws = ws.data_ptr<float>();
+  probs[0].counters = split_counters(pz::sk_tickets(probs, n), like.device());
+}
+
 const float* f32_scalar_ptr(const optional<Tensor>& t, const char* what) {
   if (!t.has_value() || !t->defined()) return nullptr;
   TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->numel() >= 1, "pz: ", what,
@@ -302,28 +322,17 @@ void gemm_op(const Tensor& A, bool a_kc, const Tensor& B, bool b_kc, const Tenso
   // 4-wave lab loop, is refused: tools/gemm_w4_lab.hip); bits 16-31: the CU budget of the persistent engine (0 = every CU)
   p.engine = static_cast<int>((flags >> 2) & 3);
   p.cus = static_cast<int>((flags >> 16) & 0xFFFF);
-  // (engine 0 with a CU budget: the persistent engine wherever it is eligible)
-  if ((p.engine >= 2 || (p.engine == 0 && (pz::sk_default() || p.cus > 0))) && pz::sk_eligible(p)) {
-    const int64_t sk_floats = pz::sk_ws_floats(&p, 1);
-    int* tickets = nullptr;
-    if (sk_floats > 0) {
-      ws = at::empty({sk_floats}, A.options().dtype(at::kFloat));
-      tickets = split_counters(pz::sk_tickets(&p, 1), A.device());
-    }
-    PZ_HIP_CHECK(pz::gemm_sk(&p, 1, sk_floats > 0 ? ws.data_ptr<float>() : nullptr, tickets, cur_stream(A)));
-    return;
+  // which engine: gemm_choose (engine 0 with PZ_GEMM_SK or a CU budget: the persistent engine
+  // wherever it is eligible)
+  if (pz::family_is(pz::gemm_choose(p, pz::gemm_knobs()), "sk")) {
+    attach_sk(&p, 1, ws, A);
+  } else {
+    TORCH_CHECK(p.engine < 2, "pz::gemm: the stream-K engine cannot run this GEMM (pz::sk_eligible)");
+    // flags bit 0: no split-K (a GEMM that runs concurrently with others: its tile count need not
+    // fill the CUs on its own, and it skips the in-launch reduction)
+    attach_split(p, (flags & 1) ? 1 : pz::gemm_split(p), ws, A);
+    TORCH_CHECK(p.mask == nullptr || pz::gemm_path(p) == 1, "pz::gemm: a mask epilogue needs an MFMA-eligible shape");
   }
-  TORCH_CHECK(p.engine < 2, "pz::gemm: the stream-K engine cannot run this GEMM (pz::sk_eligible)");
-  // flags bit 0: no split-K (a GEMM that runs concurrently with others: its tile count need not
-  // fill the CUs on its own, and it skips the in-launch reduction)
-  const int64_t ws_floats = (flags & 1) ? 0 : pz::gemm_split_ws_floats(p);
-  if (ws_floats > 0) {
-    ws = at::empty({ws_floats}, A.options().dtype(at::kFloat));
-    p.split_k = pz::gemm_split(p);
-    p.ws = ws.data_ptr<float>();
-    p.counters = split_counters(static_cast<int>(((M + 255) / 256) * ((N + 255) / 256)), A.device());
-  }
-  TORCH_CHECK(p.mask == nullptr || pz::gemm_path(p) == 1, "pz::gemm: a mask epilogue needs an MFMA-eligible shape");
   PZ_HIP_CHECK(pz::gemm(p, cur_stream(A)));
 }
 
@@ -402,13 +411,7 @@ void gemm_update_op(const Tensor& A, bool a_kc, const Tensor& B, bool b_kc, cons
   auto p = update_args(A, a_kc, B, b_kc, grad, M, N, K, alpha, params, exp_avg, exp_avg_sq, shadow, stats, amax, adam, lr,
                        beta1, beta2, eps, bias_c1, bias_c2_sqrt, grad_scale, l2, hp, epoch, stats_every);
   at::Tensor ws;
-  const int64_t ws_floats = pz::gemm_split_ws_floats(p);
-  if (ws_floats > 0) {
-    ws = at::empty({ws_floats}, A.options().dtype(at::kFloat));
-    p.split_k = pz::gemm_split(p);
-    p.ws = ws.data_ptr<float>();
-    p.counters = split_counters(static_cast<int>(((M + 255) / 256) * ((N + 255) / 256)), A.device());
-  }
+  attach_split(p, pz::gemm_split(p), ws, A);
   PZ_HIP_CHECK(pz::gemm(p, cur_stream(A)));
 }
 
@@ -435,19 +438,12 @@ int64_t gemm_pair_split_op(const Tensor& A0, const Tensor& B0, const Tensor& C0,
 }
 
 void launch_pair(pz::GemmArgs& a, pz::GemmArgs& b, const Tensor& A0) {
-  const int M0 = a.M, N0 = a.N, M1 = b.M, N1 = b.N;
   const int split = pz::gemm_pair_split(a, b);
   TORCH_CHECK(split > 0, "pz::gemm_pair: the two GEMMs cannot share a launch (check gemm_pair_split first)");
   at::Tensor ws0, ws1;  // split-K slabs, one set per GEMM
   a.split_k = b.split_k = split;
-  if (split > 1) {
-    ws0 = at::empty({(M0 / 256) * (N0 / 256) * split * 65536}, A0.options().dtype(at::kFloat));
-    ws1 = at::empty({(M1 / 256) * (N1 / 256) * split * 65536}, A0.options().dtype(at::kFloat));
-    a.ws = ws0.data_ptr<float>();
-    b.ws = ws1.data_ptr<float>();
-    a.counters = split_counters(static_cast<int>((M0 / 256) * (N0 / 256)), A0.device());
-    b.counters = split_counters(static_cast<int>((M1 / 256) * (N1 / 256)), A0.device());
-  }
+  attach_split(a, split, ws0, A0);
+  attach_split(b, split, ws1, A0);
   PZ_HIP_CHECK(pz::gemm_pair(a, b, cur_stream(A0)));
 }
 
@@ -465,14 +461,9 @@ void gemm_pair_op(const Tensor& A0, const Tensor& B0, const Tensor& C0, const Te
   if (a.engine >= 2) {
     TORCH_CHECK(pz::sk_eligible(a) && pz::sk_eligible(b), "pz::gemm_pair: the stream-K engine cannot run this pair");
     pz::GemmArgs probs[2] = {a, b};
-    const int64_t sk_floats = pz::sk_ws_floats(probs, 2);
     at::Tensor ws;
-    int* tickets = nullptr;
-    if (sk_floats > 0) {
-      ws = at::empty({sk_floats}, A0.options().dtype(at::kFloat));
-      tickets = split_counters(pz::sk_tickets(probs, 2), A0.device());
-    }
-    PZ_HIP_CHECK(pz::gemm_sk(probs, 2, sk_floats > 0 ? ws.data_ptr<float>() : nullptr, tickets, cur_stream(A0)));
+    attach_sk(probs, 2, ws, A0);
+    PZ_HIP_CHECK(pz::gemm_sk(probs, 2, probs[0].ws, probs[0].counters, cur_stream(A0)));
     return;
   }
   launch_pair(a, b, A0);

@@ -269,6 +269,21 @@ PZ_DEV void tile_coords(int wgid, int tiles_m, int tiles_n, int split, int& tm, 
   tn = in_group / gsz;
 }
 
+// Launch kernel KERN with `lds` bytes of dynamic LDS and record it in gemm_last. The attribute that
+// allows more than 64 KiB is set once per kernel: the flag is per instantiation of this template
+template <auto KERN, class Args>
+hipError_t launch_lds(const Args& args, int grid, int threads, int lds, hipStream_t s, const GemmLaunch& what) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return e;
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(KERN, dim3(grid), dim3(threads), lds, s, args);
+  gemm_last = what;
+  return hipGetLastError();
+}
+
 // tools/gemm_stamps.hip (diagnostic build only): per-workgroup s_memrealtime stamps at the phase
 // boundaries (entry, first K step landed, main loop done, epilogue start, end) + XCC id into the
 // lab's debug buffer p.dbg — where a tile's time goes (guide §7, in-kernel stamps)

@@ -190,25 +190,7 @@ PZ_DEV uint32_t relu_bits8(const u32x4_t& v) {
   return byte;
 }
 
-// Compile-time epilogue kinds. The generic epilogue (EK_ANY) carries every transform — sigmoid /
-// tanh with IEEE reciprocals, both dropout forms, aux-tile derivatives — unrolled over the tile's
-// rows: ~20k instructions, and it measured ~5 us per tile of instruction-fetch stalls with EVERY
-// transform switched off (tools/gemm_stamps.hip: stage-math phase 8.6 us in EPI_FWD with nothing
-// enabled vs 3.3 us in EPI_STORE). The MLP's stages use three shapes, each specialised to only the
-// code it runs (host: epi_kind()):
-//   EK_STORE    alpha * acc -> bf16 (weight gradients)
-//   EK_RELU     EPI_FWD with act NONE / RELU: bias, dropout pre / post, ReLU bitmask, fp8 copy
-//   EK_BWD_MASK EPI_BWD through a ReLU stage from its bitmask: dropout scales, column sums, e5m2 copy
-constexpr int EK_ANY = 0, EK_STORE = 1, EK_RELU = 2, EK_BWD_MASK = 3;
-// Fixed forward stages (EPI_FWD, no colsum, not drop_all): the activation and both dropout flags
-// are compile-time, so a row is ONE straight-line pass — no per-row flag branches, no untaken hash
-// copies. EK_RELU with every transform switched off still ran ~1,400 more VALU instructions per
-// wave and tile than the plain store (its 6.3k-instruction stage-math section: 3.6k I-cache
-// misses per launch vs 0.6k; profiles/r3_epilogue_fixed_kinds.txt). The MLP's three stage
-// shapes: linear -> ReLU -> dropout (first hidden stage), linear -> dropout -> ReLU -> dropout
-// (later hidden stages), linear -> dropout (the logits).
-constexpr int EK_F_RELU_POST = 4, EK_F_RELU_PREPOST = 5, EK_F_PRE = 6;
-constexpr bool ek_fixed(int ek) { return ek >= EK_F_RELU_POST && ek <= EK_F_PRE; }
+// The compile-time epilogue kinds EK_* and what each one specialises: gemm_dispatch.h (host: epi_kind())
 constexpr bool ek_relu(int ek) { return ek == EK_F_RELU_POST || ek == EK_F_RELU_PREPOST; }
 constexpr bool ek_pre(int ek) { return ek == EK_F_RELU_PREPOST || ek == EK_F_PRE; }
 constexpr bool ek_post(int ek) { return ek == EK_F_RELU_POST || ek == EK_F_RELU_PREPOST; }

@@ -7,7 +7,7 @@
 // 64x64 output tile, BK = 16, 256 threads (4 waves), 4x4 outputs per thread, operands staged
 // through padded LDS ([k][m+1]) so both K-major and M-major global reads coalesce.
 #include "pz_common.h"
-#include "pz_launch.h"
+#include "gemm_dispatch.h"
 
 namespace pz {
 namespace {
@@ -127,9 +127,7 @@ hipError_t launch_generic_in(const GemmArgs& p, hipStream_t s) {
 
 }  // namespace
 
-bool mfma_eligible(const GemmArgs& p);
-hipError_t gemm_mfma(const GemmArgs& p, hipStream_t s);
-bool wide_eligible(const GemmArgs& p);
+hipError_t gemm_mfma(const GemmArgs& p, const GemmLaunch& choice, hipStream_t s);
 hipError_t gemm_wide(const GemmArgs& p, hipStream_t s);
 
 hipError_t gemm_generic(const GemmArgs& p, hipStream_t s) {
@@ -142,15 +140,15 @@ hipError_t gemm_generic(const GemmArgs& p, hipStream_t s) {
   }
 }
 
-int gemm_path(const GemmArgs& p) { return mfma_eligible(p) ? 1 : (wide_eligible(p) ? 2 : 0); }
-
+// launches what gemm_choose (gemm_dispatch.h) picked; the stream-K engine takes its slabs and
+// tickets from p.ws / p.counters
 hipError_t gemm(const GemmArgs& p, hipStream_t s) {
-  if (mfma_eligible(p)) return gemm_mfma(p, s);
-  if (p.epi_mode == EPI_OPT) return hipErrorInvalidValue;  // the fused update: bf16 MFMA path only
-  if (wide_eligible(p)) return gemm_wide(p, s);
-  // bitmask / e4m3 epilogues and e4m3 operands exist on the MFMA path only
-  if (p.mask != nullptr || p.out8 != nullptr || p.in_dtype == DT_FP8) return hipErrorInvalidValue;
-  return gemm_generic(p, s);
+  const GemmLaunch choice = gemm_choose(p, gemm_knobs());
+  if (family_is(choice, "sk")) return gemm_sk(&p, 1, p.ws, p.counters, s);
+  if (family_is(choice, "mfma") || family_is(choice, "w4")) return gemm_mfma(p, choice, s);
+  if (family_is(choice, "wide")) return gemm_wide(p, s);
+  if (family_is(choice, "generic")) return gemm_generic(p, s);
+  return hipErrorInvalidValue;
 }
 
 }  // namespace pz

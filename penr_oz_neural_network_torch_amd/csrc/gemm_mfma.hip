@@ -31,11 +31,13 @@
 //    is what gemm_last reports). VAR 40 / 43, the 4-wave schedule, are in gemm_w4.h. VAR numbers
 //    in profiles/ that have no row in the table are deleted experiments: their code is in the
 //    history up to commit a839ea0.
+#include <array>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #include "pz_common.h"
-#include "pz_launch.h"
+#include "gemm_dispatch.h"
 
 namespace pz {
 namespace {
@@ -675,328 +677,60 @@ gemm_mfma_pair_kernel(const GemmPairArgs g) {
 template <int BM, int BN, int WM, int WN, bool A_KC, bool B_KC, typename OutT, typename AuxT, int VAR, int EK = EK_ANY>
 hipError_t launch_cfg(const GemmArgs& p, hipStream_t s) {
   using C = Cfg<BM, BN, WM, WN, variant(VAR).ns, variant(VAR).bk>;
-  auto kern = gemm_mfma_kernel<BM, BN, WM, WN, A_KC, B_KC, OutT, AuxT, VAR, EK>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  const int nwg = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * (p.split_k > 1 ? p.split_k : 1);
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(C::NT), C::LDS_BYTES, s, p);
-  gemm_last = {"mfma", VAR, BM, BN, EK, p.split_k > 1 ? p.split_k : 1};
-  return hipGetLastError();
-}
-
-template <int BM, int BN, int WM, int WN, typename OutT, typename AuxT, int VAR = 0>
-hipError_t launch_layout(const GemmArgs& p, hipStream_t s) {
-  if (p.a_kc && p.b_kc) return launch_cfg<BM, BN, WM, WN, true, true, OutT, AuxT, VAR>(p, s);
-  if (p.a_kc && !p.b_kc) return launch_cfg<BM, BN, WM, WN, true, false, OutT, AuxT, VAR>(p, s);
-  if (!p.a_kc && p.b_kc) return launch_cfg<BM, BN, WM, WN, false, true, OutT, AuxT, VAR>(p, s);
-  return launch_cfg<BM, BN, WM, WN, false, false, OutT, AuxT, VAR>(p, s);
+  const int split = p.split_k > 1 ? p.split_k : 1;
+  return launch_lds<&gemm_mfma_kernel<BM, BN, WM, WN, A_KC, B_KC, OutT, AuxT, VAR, EK>>(
+      p, tiles(p, BM, BN) * split, C::NT, C::LDS_BYTES, s, {"mfma", VAR, BM, BN, EK, split});
 }
 
 #ifndef PZ_GEMM_LAB  // tools/gemm_lab.hip instantiates only the variants it measures
-// buffer-addressed DMA (VAR 6) needs every staged byte within 4 GiB of the operand's base
-bool buffer_ok(const GemmArgs& p) {
-  constexpr int64_t kLim = int64_t(1) << 32;
-  const int64_t ea = (p.a_kc ? static_cast<int64_t>(p.M) : static_cast<int64_t>(p.K)) * p.lda * 2;
-  const int64_t eb = (p.b_kc ? static_cast<int64_t>(p.N) : static_cast<int64_t>(p.K)) * p.ldb * 2;
-  return ea < kLim && eb < kLim;
-}
+// The launchers of gemm_dispatch.h's kTiled, row by row and layout by layout (index 2 * a_kc +
+// b_kc; null where the row is not built for that layout): every tiled kernel the library holds
+using Launcher = hipError_t (*)(const GemmArgs&, hipStream_t);
 
-// (measured, not kept: 128x128 tiles, two workgroups per CU, instead of split-K 256x256 for
-// skinny shapes — fwd [8192,1024] K=4096 950 vs 855 TFLOP/s alone, the mlp4 step 0.9% slower)
-// 64-deep ring steps (VAR 30: 2 x 64 KiB slots, one MFMA interval = 64 MFMAs per wave, the
-// staging waves fetch whole 128-B lines of K-contiguous rows) for layouts with an M/N-contiguous
-// operand: fwd [8192,4096]x[4096,4096] +6%, dW +4%, fwd K=1024 +4% (tools/gemm_lab, same box).
-// Both operands K-contiguous (dX) stay on the 32-deep ring: the BK64 form spills there (-11%).
-bool use_bk64(const GemmArgs& p, bool buf) {
-  const int split = p.split_k > 1 ? p.split_k : 1;
-  // VAR 30 stages K-contiguous operands without a row clamp: full 256-row tiles only (which
-  // also frees the K-contiguous x K-contiguous dX GEMMs from a scratch spill: +5..6%, lab)
-  const bool full = (!p.a_kc || p.M % 256 == 0) && (!p.b_kc || p.N % 256 == 0);
-  return buf && full && p.K % 64 == 0 && (p.K / 64) % split == 0;
-}
-
-// VAR 40 for the bf16 dX layout and VAR 43 for the long-K plain fp8 forward (gemm_w4.h);
-// PZ_GEMM_W4=0 keeps those GEMMs on VAR 30 / VAR 15, 16 (A/B)
-bool w4_default() {
-  static const bool on = [] {
-    const char* e = getenv("PZ_GEMM_W4");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  return on;
-}
-
-// which specialised epilogue (gemm_epilogue.h: EK_*) covers these arguments
-int epi_kind(const GemmArgs& p) {
-  if (p.out_dtype != DT_BF16 || p.accumulate) return EK_ANY;
-  if (p.epi_mode == EPI_STORE && p.bias == nullptr && p.colsum == nullptr && p.mask == nullptr && p.out8 == nullptr)
-    return EK_STORE;
-  if (p.epi_mode == EPI_FWD && (p.epi.act == ACT_NONE || p.epi.act == ACT_RELU) && p.colsum == nullptr) {
-    const EpiSpec& e = p.epi;
-    const bool relu = e.act == ACT_RELU;
-    if (!e.drop_all) {
-      if (relu && !e.drop_pre && e.drop_post) return EK_F_RELU_POST;
-      if (relu && e.drop_pre && e.drop_post) return EK_F_RELU_PREPOST;
-      if (!relu && e.drop_pre && !e.drop_post) return EK_F_PRE;
-    }
-    return EK_RELU;
-  }
-  if (p.epi_mode == EPI_BWD && p.mask != nullptr && p.epi.act == ACT_RELU) return EK_BWD_MASK;
-  return EK_ANY;
-}
-
-// forward layout (A K-contiguous, B N-contiguous): a tile config's instantiation for epilogue kind ek
-// — the fixed stages, the ReLU stage where the config has one (RELU), else the generic epilogue
-template <int BM, int BN, int WM, int WN, typename OutT, typename AuxT, int VAR, bool RELU = true>
-hipError_t launch_fwd_kind(int ek, const GemmArgs& p, hipStream_t s) {
-  switch (ek) {
-    case EK_F_RELU_POST: return launch_cfg<BM, BN, WM, WN, true, false, OutT, AuxT, VAR, EK_F_RELU_POST>(p, s);
-    case EK_F_RELU_PREPOST: return launch_cfg<BM, BN, WM, WN, true, false, OutT, AuxT, VAR, EK_F_RELU_PREPOST>(p, s);
-    case EK_F_PRE: return launch_cfg<BM, BN, WM, WN, true, false, OutT, AuxT, VAR, EK_F_PRE>(p, s);
-    case EK_RELU:
-      if constexpr (RELU) return launch_cfg<BM, BN, WM, WN, true, false, OutT, AuxT, VAR, EK_RELU>(p, s);
-      [[fallthrough]];
-    default: return launch_cfg<BM, BN, WM, WN, true, false, OutT, AuxT, VAR>(p, s);
+template <int I, int LAY>
+constexpr Launcher tiled_launcher() {
+  constexpr TiledKey k = kTiled[I];
+  if constexpr (((k.layouts >> LAY) & 1) == 0) {
+    return nullptr;
+  } else if constexpr (k.var == 40 || k.var == 43) {
+    return &launch_w4<std::conditional_t<k.var == 40, W4Bf16, W4F8Fwd>, k.ek>;
+  } else {
+    using OutT = std::conditional_t<k.out == DT_BF16, uint16_t, float>;
+    return &launch_cfg<k.bm, k.bn, k.wm, k.wn, (LAY & 2) != 0, (LAY & 1) != 0, OutT, uint16_t, k.var, k.ek>;
   }
 }
 
-// the MLP's three GEMM layouts on the 64-deep ring, each with its stage's specialised epilogue:
-// forward X·W (K-contiguous x N-contiguous), dX = dZ·Wᵀ (both K-contiguous), dW = Xᵀ·dZ (both
-// M/N-contiguous); anything else takes the generic epilogue
-template <typename OutT, typename AuxT, int VAR>
-hipError_t launch_bk64_256(const GemmArgs& p, hipStream_t s) {
-  if constexpr (std::is_same<OutT, uint16_t>::value) {
-    const int ek = epi_kind(p);
-    if (p.a_kc && !p.b_kc) return launch_fwd_kind<256, 256, 2, 4, OutT, AuxT, VAR>(ek, p, s);
-    if (p.a_kc && p.b_kc && ek == EK_BWD_MASK)
-      return launch_cfg<256, 256, 2, 4, true, true, OutT, AuxT, VAR, EK_BWD_MASK>(p, s);
-    if (!p.a_kc && !p.b_kc && ek == EK_STORE) return launch_cfg<256, 256, 2, 4, false, false, OutT, AuxT, VAR, EK_STORE>(p, s);
-  }
-  return launch_layout<256, 256, 2, 4, OutT, AuxT, VAR>(p, s);
+template <size_t... I>
+constexpr std::array<std::array<Launcher, 4>, sizeof...(I)> tiled_launchers(std::index_sequence<I...>) {
+  return {{{tiled_launcher<I, 0>(), tiled_launcher<I, 1>(), tiled_launcher<I, 2>(), tiled_launcher<I, 3>()}...}};
+}
+constexpr auto kTiledLaunchers = tiled_launchers(std::make_index_sequence<kNumTiled>{});
+
+// launch the kernel `choice` names (gemm_choose); a choice with no row launches nothing
+hipError_t launch(const GemmLaunch& choice, const GemmArgs& p, hipStream_t s) {
+  const int row = find_row(kTiled, choice, p);
+  return row < 0 ? hipErrorInvalidValue : kTiledLaunchers[row][layout_index(p)](p, s);
 }
 
-// Fixed-kind bf16 forward GEMMs with too few 256x256 tiles to fill the CUs (the logits GEMM,
-// [8192, 1024] at K = 4096) run as 256x128 tiles on the 64-deep ring WITHOUT split-K: the
-// deterministic split-K fold's slab round trip and the split tile's heavier epilogue cost more
-// than the narrower tile's extra LDS traffic. r5 same box: fused fwd_L3 885-949 vs 830-841 TF/s,
-// mlp4 step 1.111-1.113 vs 1.130-1.138 ms (profiles/r5_ab_w128_fixed.txt). (r2, before the
-// fixed epilogue kinds and the deterministic fold: the generic-epilogue 256x128 form lost in-step.)
-bool w128_fixed(const GemmArgs& p) {
-  if (p.in_dtype != DT_BF16 || p.out_dtype != DT_BF16 || !p.a_kc || p.b_kc || p.accumulate) return false;
-  if (p.M % 256 || p.N % 128 || !ek_fixed(epi_kind(p))) return false;
-  return ((p.M / 256) * ((p.N + 255) / 256)) < 240 && (p.M / 256) * (p.N / 128) >= 240;
-}
-
-template <typename OutT, typename AuxT>
-hipError_t launch_tiles(const GemmArgs& p, hipStream_t s) {
-  auto tiles = [&](int bm, int bn) { return ((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
-  const bool buf = buffer_ok(p);
-  const bool bk64 = use_bk64(p, buf);
-  constexpr int kFill = 240;  // ~ CU count: a config below this leaves CUs idle
-  if (p.split_k > 1) {  // slabs sized for 256x256
-    if (bk64) return launch_bk64_256<OutT, AuxT, 30>(p, s);
-    if (buf) return launch_layout<256, 256, 2, 4, OutT, AuxT, 6>(p, s);
-    return launch_layout<256, 256, 2, 4, OutT, AuxT>(p, s);
-  }
-  if constexpr (std::is_same<OutT, uint16_t>::value) {
-    const int ek = epi_kind(p);
-    if (w4_default() && w4_eligible(p, ek))
-      return ek == EK_BWD_MASK ? launch_w4<W4Bf16, EK_BWD_MASK>(p, s) : launch_w4<W4Bf16, EK_STORE>(p, s);
-  }
-  // buffer-addressed LDS-DMA (VAR 6; +2..12% on the step's shapes, tools/gemm_lab)
-  if (tiles(256, 256) >= kFill) {
-    if (bk64) return launch_bk64_256<OutT, AuxT, 30>(p, s);
-    return buf ? launch_layout<256, 256, 2, 4, OutT, AuxT, 6>(p, s) : launch_layout<256, 256, 2, 4, OutT, AuxT>(p, s);
-  }
-  if (tiles(256, 128) >= kFill) {
-    if constexpr (std::is_same<OutT, uint16_t>::value) {
-      // (no ReLU-stage form of this config: w128_fixed takes the fixed kinds only)
-      if (bk64 && w128_fixed(p)) return launch_fwd_kind<256, 128, 4, 2, OutT, AuxT, 30, false>(epi_kind(p), p, s);
-    }
-    if (bk64) return launch_layout<256, 128, 4, 2, OutT, AuxT, 30>(p, s);
-    return buf ? launch_layout<256, 128, 4, 2, OutT, AuxT, 6>(p, s) : launch_layout<256, 128, 4, 2, OutT, AuxT>(p, s);
-  }
-  return buf ? launch_layout<128, 128, 2, 2, OutT, AuxT, 6>(p, s) : launch_layout<128, 128, 2, 2, OutT, AuxT>(p, s);
-}
-
-// fp8 GEMMs with at least two 256x256 tiles per CU and no split-K run as 256x128 tiles on 4-wave
-// workgroups, two per CU (VAR 16 / 17): one workgroup's epilogue beside the other's main loop
-bool f8_two_wg(const GemmArgs& p) {
-  const int t256 = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-  return p.split_k <= 1 && t256 >= 480 && p.N % 128 == 0;
-}
-
-hipError_t launch_fp8(const GemmArgs& p, hipStream_t s) {
-  const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-  if (!p.a_kc && !p.b_kc)  // e4m3 x e5m2 weight gradient (fp8_eligible: full 256-tiles, buffer-addressable,
-                          // plain store)
-    return launch_cfg<256, 256, 2, 4, false, false, uint16_t, uint16_t, 14, EK_STORE>(p, s);
-  int ek = epi_kind(p);
-  // VAR 43: the fp8 forward on the 4-wave LDS-DMA schedule, plain stores at K >= 2048 (at K = 1,024 it
-  // ties VAR 16). With the fused stage epilogues the 32x32 accumulator layout's 128-column wave rows
-  // (16 four-column groups per lane: values, column sums, bias) spill 66-213 VGPRs — the fused fp8 dX
-  // (VAR 42, tools/gemm_w4_lab_ops.h) ran 144 vs 106 us in the mlp8192 step (profiles/r6_gemm_w4.txt) —
-  // so the trainer's fused fp8 GEMMs stay on VAR 9 / 15-17
-  if (w4_default() && ek == EK_STORE && p.K >= 2048 && w4f8_fwd_eligible(p, ek)) return launch_w4<W4F8Fwd, EK_STORE>(p, s);
-  if (f8_two_wg(p)) {
-    if (p.a_kc && !p.b_kc) return launch_fwd_kind<256, 128, 2, 2, uint16_t, uint16_t, 16>(ek, p, s);
-    if (p.a_kc && p.b_kc && p.a_fmt == 1) {
-      if (ek == EK_BWD_MASK) return launch_cfg<256, 128, 2, 2, true, true, uint16_t, uint16_t, 17, EK_BWD_MASK>(p, s);
-      return launch_cfg<256, 128, 2, 2, true, true, uint16_t, uint16_t, 17>(p, s);
-    }
-  }
-  // e4m3 X x e4m3 W[in, out] (fp8_eligible: N % 256 — B's transposed image rows are whole 256-B
-  // tiles, swz_mn8 — buffer-addressable B; split-K when the tiles do not fill the CUs, gemm_split)
-  if (p.a_kc && !p.b_kc) return launch_fwd_kind<256, 256, 2, 4, uint16_t, uint16_t, 15>(ek, p, s);
-  // (measured, not kept: buffer-addressed staging, VAR 10 / 11; the 64-deep ring, VAR 12 / 13,
-  // within noise of the 32-deep one, profiles/r2_ab_fp8_bk64.txt)
-  if (ek_fixed(ek)) ek = EK_RELU;  // (VAR 8 forms: the generic ReLU-stage kind)
-  const bool big = tiles >= 240 || p.split_k > 1;
-  if (p.a_fmt == 1) {  // e5m2 x e4m3 (backward dX)
-    if (ek == EK_BWD_MASK)
-      return big ? launch_cfg<256, 256, 2, 4, true, true, uint16_t, uint16_t, 9, EK_BWD_MASK>(p, s)
-                 : launch_cfg<128, 128, 2, 2, true, true, uint16_t, uint16_t, 9, EK_BWD_MASK>(p, s);
-    return big ? launch_cfg<256, 256, 2, 4, true, true, uint16_t, uint16_t, 9>(p, s)
-               : launch_cfg<128, 128, 2, 2, true, true, uint16_t, uint16_t, 9>(p, s);
-  }
-  if (ek == EK_RELU)
-    return big ? launch_cfg<256, 256, 2, 4, true, true, uint16_t, uint16_t, 8, EK_RELU>(p, s)
-               : launch_cfg<128, 128, 2, 2, true, true, uint16_t, uint16_t, 8, EK_RELU>(p, s);
-  return big ? launch_cfg<256, 256, 2, 4, true, true, uint16_t, uint16_t, 8>(p, s)
-             : launch_cfg<128, 128, 2, 2, true, true, uint16_t, uint16_t, 8>(p, s);
-}
-
+// gemm_pair's kernels: the launchers of gemm_dispatch.h's kPair, row by row
 template <typename OutT, int VAR, int EK>
 hipError_t launch_pair_cfg(const GemmPairArgs& g, int nwg, hipStream_t s) {
   using C = Cfg<256, 256, 2, 4, variant(VAR).ns, variant(VAR).bk>;
-  auto kern = gemm_mfma_pair_kernel<256, 256, 2, 4, false, false, OutT, uint16_t, VAR, EK>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(C::NT), C::LDS_BYTES, s, g);
-  gemm_last = {"pair", VAR, 256, 256, EK, g.p[0].split_k > 1 ? g.p[0].split_k : 1};
-  return hipGetLastError();
+  return launch_lds<&gemm_mfma_pair_kernel<256, 256, 2, 4, false, false, OutT, uint16_t, VAR, EK>>(
+      g, nwg, C::NT, C::LDS_BYTES, s, {"pair", VAR, 256, 256, EK, g.p[0].split_k > 1 ? g.p[0].split_k : 1});
 }
+
+using PairLauncher = hipError_t (*)(const GemmPairArgs&, int, hipStream_t);
+template <size_t... I>
+constexpr std::array<PairLauncher, sizeof...(I)> pair_launchers(std::index_sequence<I...>) {
+  return {{&launch_pair_cfg<std::conditional_t<kPair[I].out == DT_BF16, uint16_t, float>, kPair[I].var, kPair[I].ek>...}};
+}
+constexpr auto kPairLaunchers = pair_launchers(std::make_index_sequence<kNumPair>{});
 
 #endif  // PZ_GEMM_LAB
 }  // namespace
 
 #ifndef PZ_GEMM_LAB
-bool fp8_dw_eligible(const GemmArgs& p) {  // VAR 14: X8ᵀ (e4m3) · dZ8 (e5m2), both M/N-contiguous
-  if (p.a_fmt != 0 || p.b_fmt != 1 || p.epi_mode != EPI_STORE || p.accumulate) return false;
-  if (p.bias != nullptr || p.colsum != nullptr || p.mask != nullptr || p.out8 != nullptr || p.aux != nullptr) return false;
-  if (p.M % 256 != 0 || p.N % 256 != 0 || p.K % 64 != 0 || p.K < 64) return false;
-  if (p.lda % 16 != 0 || p.ldb % 16 != 0 || p.ldc % 8 != 0) return false;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if (!al16(p.A) || !al16(p.B) || !al16(p.C)) return false;
-  constexpr int64_t kLim = int64_t(1) << 32;  // buffer-addressed staging
-  return static_cast<int64_t>(p.K) * p.lda < kLim && static_cast<int64_t>(p.K) * p.ldb < kLim;
-}
-
-bool fp8_eligible(const GemmArgs& p) {
-  if (p.force_generic || p.in_dtype != DT_FP8 || p.out_dtype != DT_BF16) return false;
-  if (p.bias64 != nullptr || p.colsum64 != nullptr) return false;
-  if (!p.a_kc && !p.b_kc) return fp8_dw_eligible(p);
-  if (p.b_fmt != 0) return false;
-  if (p.a_kc && !p.b_kc) {  // VAR 15: forward on the [in, out] e4m3 weights
-    if (p.a_fmt != 0 || p.epi_mode == EPI_BWD || p.accumulate || p.N % 256 != 0) return false;
-    if (static_cast<int64_t>(p.K) * p.ldb >= (int64_t(1) << 32)) return false;  // buffer-addressed B
-  } else if (!p.a_kc || p.accumulate) {
-    return false;
-  }
-  if (p.M < 64 || p.N < 64 || p.K < 64 || p.K % 64 != 0) return false;
-  if (p.N % 8 != 0 || p.ldc % 8 != 0 || p.lda % 16 != 0 || p.ldb % 16 != 0) return false;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if (!al16(p.A) || !al16(p.B) || !al16(p.C)) return false;
-  if (p.idx_ld % 2 != 0) return false;
-  if (p.bias != nullptr && !al16(p.bias)) return false;
-  // e4m3 x e4m3: forward stages; e5m2 (A, gradients) x e4m3 (B): backward dX stages only
-  if ((p.a_fmt == 1) != (p.epi_mode == EPI_BWD)) return false;
-  if (p.out8 != nullptr && p.out8_fmt != (p.epi_mode == EPI_BWD ? 1 : 0)) return false;
-  if (p.epi_mode == EPI_BWD && p.mask == nullptr &&
-      (p.aux == nullptr || p.aux_dtype != DT_BF16 || p.ldaux % 8 != 0 || (reinterpret_cast<uintptr_t>(p.aux) & 15)))
-    return false;
-  if (p.mask != nullptr && (p.ldmask % 32 != 0 || (reinterpret_cast<uintptr_t>(p.mask) & 7) != 0)) return false;
-  if (p.out8 != nullptr && (p.ldout8 % 8 != 0 || (reinterpret_cast<uintptr_t>(p.out8) & 7) != 0 ||
-                            p.out8_qscale == nullptr))
-    return false;
-  return true;
-}
-
-bool mfma_eligible(const GemmArgs& p) {
-  if (p.in_dtype == DT_FP8) return fp8_eligible(p);
-  if (p.force_generic || p.in_dtype != DT_BF16) return false;
-  if (p.bias64 != nullptr || p.colsum64 != nullptr) return false;  // fp64 models: wide / generic paths
-  if (p.out_dtype != DT_BF16 && p.out_dtype != DT_F32) return false;
-  if (p.M < 64 || p.N < 64 || p.K < kBK || p.K % kBK != 0) return false;
-  if (p.N % 8 != 0 || p.ldc % 8 != 0) return false;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if (!al16(p.A) || !al16(p.B) || !al16(p.C)) return false;
-  if (p.lda % 8 != 0 || p.ldb % 8 != 0) return false;
-  if (!p.a_kc && p.M % 8 != 0) return false;
-  if (p.idx_ld % 2 != 0) return false;  // 4-element epilogue groups start at even element indices
-  // fused stage epilogues: bf16 output only; accumulate: fp32 output only
-  if (p.out_dtype == DT_F32 && p.epi_mode != EPI_STORE && p.epi_mode != EPI_OPT) return false;
-  if (p.epi_mode == EPI_OPT) {  // fused optimizer update: plain gradient tiles, 16-B state vectors
-    if (p.out_dtype != DT_F32 || p.bias != nullptr || p.colsum != nullptr || p.accumulate || p.mask != nullptr ||
-        p.out8 != nullptr || p.ldc % 4 != 0 || p.opt.params == nullptr || !al16(p.opt.params))
-      return false;
-    if (p.opt.adam && (!al16(p.opt.exp_avg) || !al16(p.opt.exp_avg_sq))) return false;
-    if (p.opt.shadow != nullptr &&
-        (reinterpret_cast<uintptr_t>(p.opt.shadow) & (p.opt.shadow_dtype == DT_BF16 ? 7 : 15)) != 0)
-      return false;
-  }
-  if (p.out_dtype == DT_BF16 && p.accumulate) return false;
-  if (p.bias != nullptr && !al16(p.bias)) return false;
-  if (p.out8 != nullptr && (p.out_dtype != DT_BF16 || p.out8_fmt != (p.epi_mode == EPI_BWD ? 1 : 0) ||
-                            (p.epi_mode != EPI_BWD && p.epi_mode != EPI_FWD) || p.ldout8 % 8 != 0 ||
-                            (reinterpret_cast<uintptr_t>(p.out8) & 7) != 0 || p.out8_qscale == nullptr))
-    return false;
-  if (p.mask != nullptr) {
-    if (p.out_dtype != DT_BF16 || p.ldmask % 32 != 0 || (reinterpret_cast<uintptr_t>(p.mask) & 7) != 0) return false;
-    if (p.epi_mode == EPI_BWD ? p.epi.act != ACT_RELU : p.epi_mode != EPI_FWD) return false;
-    return true;
-  }
-  if (p.epi_mode == EPI_BWD) {
-    if (p.aux == nullptr || p.ldaux % 8 != 0 || !al16(p.aux)) return false;
-    if (p.aux_dtype != DT_BF16) return false;
-  }
-  return true;
-}
-
-int gemm_split(const GemmArgs& p) {
-  // fp8 skinny shapes run better as 128x128 tiles (measured: split-K 256x256 -4%); the fp8
-  // weight-gradient GEMM (both operands M/N-contiguous, 256-tiles only) splits like bf16
-  // (and the N-contiguous-weight fp8 forward, VAR 15: 256x256 tiles only)
-  const bool f8_dw = p.in_dtype == DT_FP8 && !p.b_kc;
-  if ((p.in_dtype == DT_FP8 && !f8_dw) || !mfma_eligible(p)) return 1;
-  if (w128_fixed(p)) return 1;
-  const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-  constexpr int kFill = 240;
-  if (tiles >= kFill) return 1;
-  // (fixed-kind forwards: 256x128 tiles instead, w128_fixed above; the generic-epilogue kinds
-  // keep the split — r2: 1008 vs 881 TF/s alone but the mlp4 step slower,
-  // profiles/r2_lab_skinny_fwd.txt)
-  const int nk = p.K / (p.in_dtype == DT_FP8 ? 64 : kBK);
-  for (int sp : {2, 4, 8})
-    if (tiles * sp >= kFill && nk % sp == 0 && nk / sp >= 16) return sp;
-  return 1;
-}
-
-int64_t gemm_split_ws_floats(const GemmArgs& p) {
-  const int sp = gemm_split(p);
-  if (sp <= 1) return 0;
-  return static_cast<int64_t>((p.M + 255) / 256) * ((p.N + 255) / 256) * sp * 256 * 256;
-}
-
 // whole-tile epilogue stores write through (sc1) instead of leaving dirty L2 lines for the kernel
 // boundary's write-back (GemmArgs::store_wt); on by default, PZ_GEMM_WT=0 turns it off. r4 A/B,
 // mlp4 step: 1.1112 ms off, 1.1081 on; with PZ_OPT_NT on 1.1023 -> 1.0975
@@ -1008,32 +742,10 @@ int store_wt_default() {
   return on;
 }
 
-// gemm_pair: both GEMMs in the weight-gradient layout (A and B M/N-contiguous), plain stores of
-// whole 256 x 256 tiles, one K; returns the split-K factor of the pair, or 0 if it cannot be paired
-int gemm_pair_split(const GemmArgs& a, const GemmArgs& b) {
-  for (const GemmArgs* q : {&a, &b}) {
-    const GemmArgs& p = *q;
-    if (p.a_kc || p.b_kc || p.epi_mode != EPI_STORE || p.accumulate || p.force_generic) return 0;
-    if (p.bias || p.colsum || p.mask || p.out8 || p.aux || p.bias64 || p.colsum64) return 0;
-    if (p.M % 256 || p.N % 256 || p.K % 64 || !mfma_eligible(p)) return 0;
-    if (p.in_dtype != DT_FP8 && (!buffer_ok(p) || epi_kind(p) != (p.out_dtype == DT_BF16 ? EK_STORE : EK_ANY)))
-      return 0;
-  }
-  if (a.K != b.K || a.in_dtype != b.in_dtype || a.out_dtype != b.out_dtype || a.a_fmt != b.a_fmt ||
-      a.b_fmt != b.b_fmt)
-    return 0;
-  if (a.in_dtype == DT_FP8 && a.out_dtype != DT_BF16) return 0;
-  const int tiles = (a.M / 256) * (a.N / 256) + (b.M / 256) * (b.N / 256);
-  const int nk = a.K / 64;
-  constexpr int kFill = 240;
-  for (int sp : {1, 2, 4, 8})
-    if (tiles * sp >= kFill && nk % sp == 0 && nk / sp >= 16) return sp;
-  return nk % 8 == 0 && nk / 8 >= 16 ? 8 : 1;
-}
-
 hipError_t gemm_pair(const GemmArgs& a, const GemmArgs& b, hipStream_t s) {
-  const int split = gemm_pair_split(a, b);
-  if (split == 0 || a.split_k != split || b.split_k != split) return hipErrorInvalidValue;
+  const GemmLaunch choice = gemm_pair_choose(a, b);
+  const int split = choice.split, row = find_row(kPair, choice, a);
+  if (row < 0 || a.split_k != split || b.split_k != split) return hipErrorInvalidValue;
   if (split > 1 && (a.ws == nullptr || a.counters == nullptr || b.ws == nullptr || b.counters == nullptr))
     return hipErrorInvalidValue;
   GemmPairArgs g;
@@ -1041,21 +753,17 @@ hipError_t gemm_pair(const GemmArgs& a, const GemmArgs& b, hipStream_t s) {
   g.p[1] = b;
   g.p[0].store_wt = g.p[1].store_wt = store_wt_default();
   g.p[0].prio = g.p[1].prio = 1;
-  g.nwg0 = (a.M / 256) * (a.N / 256) * split;
-  const int nwg = g.nwg0 + (b.M / 256) * (b.N / 256) * split;
-  if (a.in_dtype == DT_FP8) return launch_pair_cfg<uint16_t, 14, EK_STORE>(g, nwg, s);
-  if (a.out_dtype == DT_BF16) return launch_pair_cfg<uint16_t, 30, EK_STORE>(g, nwg, s);
-  return launch_pair_cfg<float, 30, EK_ANY>(g, nwg, s);
+  g.nwg0 = tiles(a, 256, 256) * split;
+  return kPairLaunchers[row](g, g.nwg0 + tiles(b, 256, 256) * split, s);
 }
 
-hipError_t gemm_mfma(const GemmArgs& in, hipStream_t s) {
+// launches the tiled kernel gemm_choose picked for `in` (family "mfma" or "w4")
+hipError_t gemm_mfma(const GemmArgs& in, const GemmLaunch& choice, hipStream_t s) {
   GemmArgs p = in;
   p.store_wt = store_wt_default();
   p.prio = 1;
   if (p.split_k > 1 && (p.ws == nullptr || p.counters == nullptr)) return hipErrorInvalidValue;
-  if (p.in_dtype == DT_FP8) return launch_fp8(p, s);
-  if (p.out_dtype == DT_BF16) return launch_tiles<uint16_t, uint16_t>(p, s);
-  return launch_tiles<float, uint16_t>(p, s);
+  return launch(choice, p, s);
 }
 #endif  // PZ_GEMM_LAB
 

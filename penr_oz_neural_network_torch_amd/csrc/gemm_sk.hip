@@ -37,7 +37,7 @@
 #include <type_traits>
 
 #include "pz_common.h"
-#include "pz_launch.h"
+#include "gemm_dispatch.h"
 
 namespace pz {
 namespace {
@@ -67,7 +67,6 @@ constexpr int kSkStampUnits = 6;
 
 constexpr int kSkB = 256;                    // macro tile BM = BN
 constexpr int kSkSlab = kSkB * kSkB;         // fp32 floats of one partial tile
-constexpr int kSkF32 = 100;                  // epilogue code of the fp32-output store path
 constexpr int kSkLds = 128 * 1024;           // both main loops' rings = the epilogue's C image
 
 // Main-loop geometry (W = 8 waves): two waves per SIMD, 128x64 wave tiles, the ping-pong over a
@@ -81,6 +80,8 @@ template <int W> struct SkGeo {
   static constexpr int BK = 64;              // K depth of one schedule step
   static constexpr int CH = 8 * TN;          // f32x4 accumulator chunks per lane
 };
+
+static_assert(kSkB == 256 && SkGeo<8>::BK == 64, "sk_eligible (gemm_dispatch.h) states the tile and the K step");
 
 struct SkSched {
   int nprob;
@@ -425,39 +426,6 @@ int device_cus() {
   return n;
 }
 
-// which epilogue covers these arguments (-1: none on this engine)
-int sk_epi_kind(const GemmArgs& p) {
-  if (p.out_dtype == DT_F32) {
-    if (p.epi_mode != EPI_STORE || p.mask != nullptr || p.out8 != nullptr || p.colsum != nullptr) return -1;
-    return kSkF32;
-  }
-  if (p.out_dtype != DT_BF16 || p.accumulate) return -1;
-  if (p.epi_mode == EPI_STORE) {
-    if (p.out8 != nullptr) return -1;
-    return (p.bias == nullptr && p.colsum == nullptr && p.mask == nullptr) ? EK_STORE : EK_ANY;
-  }
-  if (p.epi_mode == EPI_FWD) {
-    const EpiSpec& e = p.epi;
-    if ((e.act == ACT_NONE || e.act == ACT_RELU) && p.colsum == nullptr) {
-      const bool relu = e.act == ACT_RELU;
-      if (!e.drop_all) {
-        if (relu && !e.drop_pre && e.drop_post) return EK_F_RELU_POST;
-        if (relu && e.drop_pre && e.drop_post) return EK_F_RELU_PREPOST;
-        if (!relu && e.drop_pre && !e.drop_post) return EK_F_PRE;
-      }
-      return EK_RELU;
-    }
-    return EK_ANY;
-  }
-  if (p.epi_mode == EPI_BWD) {
-    if (p.mask != nullptr) return p.epi.act == ACT_RELU ? EK_BWD_MASK : -1;
-    if (p.aux == nullptr || p.aux_dtype != DT_BF16 || p.ldaux % 8 != 0 || (reinterpret_cast<uintptr_t>(p.aux) & 15))
-      return -1;
-    return EK_ANY;
-  }
-  return -1;
-}
-
 SkSched sk_plan(const GemmArgs* probs, int n) {
   SkSched s{};
   s.nprob = n;
@@ -484,16 +452,8 @@ SkSched sk_plan(const GemmArgs* probs, int n) {
 
 template <bool AKC, bool BKC, typename OutT, int EK, int W>
 hipError_t sk_launch(const SkArgs& a, hipStream_t st) {
-  auto kern = gemm_sk_kernel<AKC, BKC, OutT, EK, W>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kSkLds);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(a.s.grid), dim3(SkGeo<W>::NT), kSkLds, st, a);
-  gemm_last = {"sk", 0, kSkB, kSkB, EK, 1};
-  return hipGetLastError();
+  return launch_lds<&gemm_sk_kernel<AKC, BKC, OutT, EK, W>>(a, a.s.grid, SkGeo<W>::NT, kSkLds, st,
+                                                            {"sk", 0, kSkB, kSkB, EK, 1});
 }
 
 hipError_t sk_dispatch(const SkArgs& a, int ek, hipStream_t st) {
@@ -529,44 +489,6 @@ hipError_t sk_dispatch(const SkArgs& a, int ek, hipStream_t st) {
 
 }  // namespace
 
-bool sk_default() {
-  static const bool on = [] {
-    const char* e = getenv("PZ_GEMM_SK");
-    return e != nullptr && atoi(e) != 0;
-  }();
-  return on;
-}
-
-bool deterministic() {
-  static const bool on = [] {
-    const char* e = getenv("PZ_DETERMINISTIC");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  return on;
-}
-
-bool sk_eligible(const GemmArgs& p) {
-  if (p.force_generic || p.in_dtype != DT_BF16 || (p.out_dtype != DT_BF16 && p.out_dtype != DT_F32)) return false;
-  if (p.bias64 != nullptr || p.colsum64 != nullptr) return false;
-  constexpr int bk = SkGeo<8>::BK;
-  if (p.engine == 3) return false;  // (round-5 lab loop: tools/gemm_w4_lab.hip)
-  if (p.M <= 0 || p.N <= 0 || p.M % kSkB != 0 || p.N % kSkB != 0 || p.K % bk != 0 || p.K < 2 * bk) return false;
-  if (!p.a_kc && p.b_kc) return false;  // (no MLP GEMM has this layout)
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if (!al16(p.A) || !al16(p.B) || (p.C != nullptr && !al16(p.C))) return false;
-  if (p.lda % 8 != 0 || p.ldb % 8 != 0 || p.ldc % 8 != 0 || p.idx_ld % 2 != 0) return false;
-  if (p.bias != nullptr && !al16(p.bias)) return false;
-  constexpr int64_t kLim = int64_t(1) << 32;  // buffer-addressed staging: 32-bit byte offsets
-  if ((p.a_kc ? static_cast<int64_t>(p.M) : static_cast<int64_t>(p.K)) * p.lda * 2 >= kLim) return false;
-  if ((p.b_kc ? static_cast<int64_t>(p.N) : static_cast<int64_t>(p.K)) * p.ldb * 2 >= kLim) return false;
-  if (p.mask != nullptr && (p.ldmask % 32 != 0 || (reinterpret_cast<uintptr_t>(p.mask) & 15) != 0)) return false;
-  if (p.out8 != nullptr && (p.out8_fmt != (p.epi_mode == EPI_BWD ? 1 : 0) || p.ldout8 % 8 != 0 ||
-                            (reinterpret_cast<uintptr_t>(p.out8) & 7) != 0 || p.out8_qscale == nullptr))
-    return false;
-  const int ek = sk_epi_kind(p);
-  return ek >= 0;
-}
-
 int sk_tickets(const GemmArgs* probs, int n) { return sk_plan(probs, n).sk_tiles; }
 
 int64_t sk_ws_floats(const GemmArgs* probs, int n) {
@@ -578,9 +500,9 @@ hipError_t gemm_sk(const GemmArgs* probs, int n, float* ws, int* counters, hipSt
   if (n < 1 || n > 2) return hipErrorInvalidValue;
   for (int i = 0; i < n; ++i)
     if (!sk_eligible(probs[i])) return hipErrorInvalidValue;
-  const int ek = sk_epi_kind(probs[0]);
+  const int ek = sk_takes(probs[0], epi_kind(probs[0]));
   if (n == 2 && (probs[1].K != probs[0].K || probs[1].a_kc != probs[0].a_kc || probs[1].b_kc != probs[0].b_kc ||
-                 sk_epi_kind(probs[1]) != ek || probs[1].out_dtype != probs[0].out_dtype))
+                 sk_takes(probs[1], epi_kind(probs[1])) != ek || probs[1].out_dtype != probs[0].out_dtype))
     return hipErrorInvalidValue;
   SkArgs a{};
   for (int i = 0; i < n; ++i) {

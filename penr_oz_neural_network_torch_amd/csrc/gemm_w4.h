@@ -25,7 +25,8 @@
 //   mma(acc, b, a); alpha(p): the epilogue's factor;
 //   NB, b_class(i): B's per-lane DMA offsets and the one piece i (0..7) of a K step uses;
 //   M/N-contiguous B only: B_ROWS (k-rows per 1-KiB piece), b_lane(c, lane, ldb), frag_b(slot, kh, col0, f, lane).
-// The library dispatches W4Bf16 (VAR 40) and W4F8Fwd (VAR 43) below; the measured, undispatched
+// The library dispatches W4Bf16 (VAR 40) and W4F8Fwd (VAR 43) below, for the GEMMs that w4_eligible /
+// w4f8_fwd_eligible (gemm_dispatch.h) accept; the measured, undispatched
 // VAR 41 / 42 live in tools/gemm_w4_lab_ops.h.
 namespace w4cfg {
 constexpr int kW4M = 256, kW4N = 256, kW4T = 256;
@@ -178,26 +179,8 @@ w4_kernel(const GemmArgs p) {
 
 template <class Ops, int EK>
 hipError_t launch_w4(const GemmArgs& p, hipStream_t s) {
-  auto kern = w4_kernel<Ops, EK>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       2 * w4cfg::kTB);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((p.M / w4cfg::kW4M) * (p.N / w4cfg::kW4N)), dim3(w4cfg::kW4T), 2 * w4cfg::kTB, s, p);
-  gemm_last = {"w4", Ops::VAR, w4cfg::kW4M, w4cfg::kW4N, EK, 1};
-  return hipGetLastError();
-}
-
-// the shape conditions of every variant: whole 256 x 256 tiles that fill the CUs, no split-K, at
-// least 2 K steps of `step` elements, buffer-addressable operands (their extents in bytes)
-inline bool w4_shape_ok(const GemmArgs& p, int step, int64_t a_bytes, int64_t b_bytes) {
-  if (p.split_k > 1 || p.M % 256 || p.N % 256 || p.K % step || p.K < 2 * step) return false;
-  if ((p.M / 256) * (p.N / 256) < 240) return false;
-  constexpr int64_t kLim = int64_t(1) << 32;
-  return a_bytes < kLim && b_bytes < kLim;
+  return launch_lds<&w4_kernel<Ops, EK>>(p, (p.M / w4cfg::kW4M) * (p.N / w4cfg::kW4N), w4cfg::kW4T, 2 * w4cfg::kTB, s,
+                                         {"w4", Ops::VAR, w4cfg::kW4M, w4cfg::kW4N, EK, 1});
 }
 
 // VAR 40 — the bf16 dX GEMM (both operands K-contiguous) on v_mfma_f32_16x16x32_bf16.
@@ -219,13 +202,6 @@ struct W4Bf16 {
   }
   static PZ_DEV float alpha(const GemmArgs& p) { return p.alpha; }
 };
-
-// dX-layout bf16 GEMMs VAR 40 takes: a backward-mask or plain-store epilogue
-inline bool w4_eligible(const GemmArgs& p, int ek) {
-  if (!p.a_kc || !p.b_kc || p.in_dtype != DT_BF16 || p.out_dtype != DT_BF16 || p.accumulate) return false;
-  if (ek != EK_BWD_MASK && ek != EK_STORE) return false;
-  return w4_shape_ok(p, 64, static_cast<int64_t>(p.M) * p.lda * 2, static_cast<int64_t>(p.N) * p.ldb * 2);
-}
 
 // VAR 43 — the fp8 forward X8 (e4m3, K-contiguous) x W8 (e4m3 [in, out], N-contiguous) on
 // v_mfma_scale_f32_32x32x64_f8f6f4 (unit E8M0 block scales; the per-tensor dequant scales go into
@@ -265,12 +241,3 @@ struct W4F8Fwd {
     return p.alpha * (p.scale_a != nullptr ? *p.scale_a : 1.f) * (p.scale_b != nullptr ? *p.scale_b : 1.f);
   }
 };
-
-// the fp8 forward GEMMs VAR 43 takes (e4m3 x e4m3 [in, out] weights)
-inline bool w4f8_fwd_eligible(const GemmArgs& p, int ek) {
-  if (!p.a_kc || p.b_kc || p.in_dtype != DT_FP8 || p.a_fmt != 0 || p.b_fmt != 0 || p.out_dtype != DT_BF16 ||
-      p.accumulate || p.epi_mode == EPI_BWD)
-    return false;
-  if (!ek_fixed(ek) && ek != EK_RELU && ek != EK_STORE) return false;
-  return w4_shape_ok(p, 128, static_cast<int64_t>(p.M) * p.lda, static_cast<int64_t>(p.K) * p.ldb);
-}

@@ -246,14 +246,7 @@ hipError_t launch_wide_in(const GemmArgs& p, hipStream_t s) {
 
 }  // namespace
 
-// fp32 / fp64 operands on the matrix cores; tiny problems (one partial tile, e.g. the
-// reference's 9x9 tic-tac-toe layers) stay on the generic VALU tile, which wastes fewer lanes
-bool wide_eligible(const GemmArgs& p) {
-  if (p.force_generic || (p.in_dtype != DT_F32 && p.in_dtype != DT_F64)) return false;
-  if (p.mask != nullptr || p.out8 != nullptr || p.split_k > 1 || p.epi_mode == EPI_OPT) return false;
-  return static_cast<int64_t>(p.M) * p.N >= 64 * 64 && p.K >= 16;
-}
-
+// (which GEMMs run here: wide_eligible, gemm_dispatch.h)
 hipError_t gemm_wide(const GemmArgs& p, hipStream_t s) {
   if (p.M <= 0 || p.N <= 0) return hipSuccess;
   if (p.in_dtype == DT_F64) return launch_wide_in<double>(p, s);

@@ -117,6 +117,9 @@ struct GemmArgs {
   int engine;
 };
 
+// The functions below that decide something (sk_eligible, sk_default, deterministic, gemm_split,
+// gemm_split_ws_floats, gemm_pair_split, gemm_path) are defined inline in gemm_dispatch.h, beside
+// gemm_choose: a caller includes that header.
 // persistent stream-K engine: eligibility, workspace (fp32 floats for the partial-tile slabs of a
 // `cus`-workgroup launch; 0 = none needed) and launch over one or two problems of one layout and
 // epilogue kind (the second one's tiles follow the first's; equal K)
@@ -144,9 +147,9 @@ hipError_t gemm_pair(const GemmArgs& a, const GemmArgs& b, hipStream_t stream);
 int gemm_path(const GemmArgs& args);  // 0 = generic VALU, 1 = MFMA bf16 / fp8, 2 = MFMA fp32 / fp64
 
 // The GEMM kernel this thread launched last. Every launcher writes it next to its launch, so it
-// cannot disagree with what ran (gemm_path only predicts the path): family "generic", "wide",
+// cannot disagree with what ran (gemm_choose, gemm_dispatch.h, predicts it): family "generic", "wide",
 // "mfma" (the tiled kernels), "w4" (gemm_w4.h), "sk" (stream-K) or "pair"; the kernel's VAR number
-// (0 where the family has none), output tile, epilogue kind (gemm_epilogue.h EK_*; 0 = EK_ANY where
+// (0 where the family has none), output tile, epilogue kind (gemm_dispatch.h EK_*; 0 = EK_ANY where
 // the family has none) and split-K factor
 struct GemmLaunch {
   const char* family;

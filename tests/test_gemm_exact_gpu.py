@@ -34,13 +34,13 @@ Dispatch cells reached (kFill = 240):
                                     (fp64 bounds: run_case; the fp32 / fp64 matrix-core kernel runs through
                                     run_case from test_gemm_wide_exact_gpu.py)
   sk/var0/256x256/ek1|3|4|5|6|100    (1536, 1280, 512) on 37 CUs (30 data-parallel tiles) and 200 (two K halves)
-Not reached on purpose: the !buffer_ok fallbacks (VAR 0; need a 4 GiB operand), fp32 outputs of the
+Not reached on purpose: the !buffer_addressable fallbacks (VAR 0; need a 4 GiB operand), fp32 outputs of the
 stream-K engine outside the dW layout (it has none). fp8 operands run through this file's run_case
 from test_gemm_fp8_exact_gpu.py (its ``fmts`` / ``layout`` / ``q8`` arguments); gemm_pair and
 gemm_update (EPI_OPT) are in test_gemm_pair_update_gpu.py.
 
 Measured on MI355X (the file takes about 17 s): every kernel name above as predicted from
-launch_tiles, every none / ReLU form at p = 0.5 and 1.0 exact. Worst err / bound: p = 0.3 kept values
+gemm_choose, every none / ReLU form at p = 0.5 and 1.0 exact. Worst err / bound: p = 0.3 kept values
 0.987 (the bound has no slack: a bf16 rounding alone reaches 2^-8 |ref| just above a power of two,
 its unit roundoff is 2^-8, not 2^-9), their colsum 0.013; sigmoid / tanh forward 0.994 (the same bf16
 rounding), backward 0.993 with colsum 0.005.
@@ -172,7 +172,7 @@ def epi_kind(f: Form) -> int:
 
 
 def expected_kernel(cls: str, form: str, no_split: bool = False) -> str:
-    """gemm_last_kernel() of shape class ``cls`` x form, read off launch_tiles / gemm_split."""
+    """gemm_last_kernel() of shape class ``cls`` x form, read off gemm_choose (csrc/gemm_dispatch.h: choose_bf16) / gemm_split."""
     f, ek = FORMS[form], epi_kind(FORMS[form])
     if cls == "S128" or no_split:
         return "mfma/var6/128x128/ek0/split1"

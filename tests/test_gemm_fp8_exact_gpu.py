@@ -1,4 +1,4 @@
-"""The fp8 GEMMs (launch_fp8 in csrc/gemm_mfma.hip: VAR 8, 9, 14, 15, 16, 17; VAR 43 in csrc/gemm_w4.h),
+"""The fp8 GEMMs (choose_fp8 in csrc/gemm_dispatch.h; csrc/gemm_mfma.hip: VAR 8, 9, 14, 15, 16, 17; VAR 43 in csrc/gemm_w4.h),
 value for value, on every dispatch cell and epilogue form.
 
 Method: test_gemm_exact_gpu's, through its run_case. The operands hold integers in [-4, 4] (exact in
@@ -17,7 +17,7 @@ epilogue takes it from the stored bf16 values, as the bf16 kernels do).
 The fp8 copy runs at three factors: 2^-3 (the bf16 test's; e4m3 saturates there), "sat" (e5m2: 2^8,
 some |y| q pass 57344) and "sub" (2^-8 / 2^-16: some outputs land on subnormal codes).
 
-Dispatch cells, as gemm_last_kernel() named them on MI355X (all as read from launch_fp8, fp8_eligible,
+Dispatch cells, as gemm_last_kernel() named them on MI355X (all as read from gemm_choose (choose_fp8), fp8_eligible,
 f8_two_wg, gemm_split and w4_shape_ok; no shape of the plan had to change):
   mfma/var8/128x128/ek0|2/split1    e4m3 x e4m3, both K-contiguous, (200, 136, 192): every forward form
   mfma/var8/256x256/ek0|2/split1    (4096, 3840, 64) and ragged (4088, 3832, 64); the fixed kinds run as ek2
@@ -64,7 +64,7 @@ BWD_FORMS = [f for f in DX_FORMS if FORMS[f].mode == PF.EPI_BWD]   # e5m2 operan
 
 
 def expected_kernel(cell, shape, form, no_split=False):
-    """gemm_last_kernel() of an fp8 launch, read off launch_fp8."""
+    """gemm_last_kernel() of an fp8 launch, read off gemm_choose (csrc/gemm_dispatch.h: choose_fp8)."""
     M, N, K = shape
     ek = epi_kind(FORMS[form])
     t256 = -(-M // 256) * -(-N // 256)
@@ -138,7 +138,7 @@ def test_fp8_gemm_is_exact(native_lib, cell, shape, form):
 
 
 def test_table_reaches_every_cell():
-    """The kernel names the table expects (each launch asserts its own) cover the dispatch of launch_fp8."""
+    """The kernel names the table expects (each launch asserts its own) cover the dispatch of gemm_choose for fp8 operands (choose_fp8)."""
     names = {expected_kernel(*t) for t in TABLE}
     want = {f"mfma/var8/{t}/ek{k}/split1" for t in ("128x128", "256x256") for k in (0, 2)}
     want |= {f"mfma/var9/{t}/ek{k}/split1" for t in ("128x128", "256x256") for k in (0, 3)}

@@ -21,7 +21,7 @@ gemm_update. torch.ops.pz.gemm_update with integer bf16 operands: the gradient i
   stats_every = 2 at an even and an odd epoch; stats = amax = None; the hp table's row `epoch`.
   Strided state: params, m, v and shadow as column slices [:, 8 : 8 + N] of buffers 16 columns wider and
   8 rows taller, every byte outside the slices unchanged.
-Kernel names (launch_tiles<float>): (256, 256, 64), (200, 136, 96) and (512, 4096, 512)
+Kernel names (gemm_choose, fp32 C): (256, 256, 64), (200, 136, 96) and (512, 4096, 512)
 mfma/var6/128x128/ek0/split1; (4088, 3832, 64) mfma/var30/256x256/ek0/split1; (1536, 1280, 4096) and the
 ragged-M (1528, 1280, 4096) mfma/var30/256x256/ek0/split8.
 

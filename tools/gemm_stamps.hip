@@ -58,7 +58,7 @@ static double med(std::vector<double> v) {
 int main(int argc, char** argv) {
   const int B = 8192;
   using F = LaunchFn;
-  // the library's dispatch (gemm_mfma.hip: launch_bk64_256 / launch_fp8): each stage's GEMM with its
+  // the library's dispatch (gemm_dispatch.h: gemm_choose): each stage's GEMM with its
   // specialised epilogue (EK_*); *_gen = the same GEMM on the generic epilogue (A/B)
   constexpr int R = EK_RELU, S = EK_STORE, M = EK_BWD_MASK, G = EK_ANY;
   constexpr int F1 = EK_F_RELU_POST, F2 = EK_F_RELU_PREPOST, F3 = EK_F_PRE;  // fixed forward kinds
