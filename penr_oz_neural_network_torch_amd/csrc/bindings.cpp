@@ -594,6 +594,21 @@ void gemm_skinny_w8_op(const Tensor& x, const Tensor& w8, const Tensor& scale, c
   PZ_HIP_CHECK(pz::gemm_skinny_w8(a, cur_stream(x)));
 }
 
+// (strips, slices, slice_len) of the K-split plan a skinny GEMM of this shape runs with: what
+// pz::skinny_plan / pz::skinny_w8_plan return, nothing launched. dtype: pz::DT_BF16 or pz::DT_F32.
+std::vector<int64_t> plan_triple(const pz::SkinnyPlan& p) { return {p.strips, p.slices, p.slice_len}; }
+
+std::vector<int64_t> gemm_skinny_plan_op(int64_t K, int64_t N, int64_t dtype) {
+  TORCH_CHECK(K >= 1 && N >= 1 && K <= INT32_MAX && N <= INT32_MAX, "pz::gemm_skinny_plan: K and N must be positive ints");
+  TORCH_CHECK(dtype == pz::DT_BF16 || dtype == pz::DT_F32, "pz::gemm_skinny_plan: bf16 / fp32 operands only");
+  return plan_triple(pz::skinny_plan(static_cast<int>(K), static_cast<int>(N), static_cast<int>(dtype)));
+}
+
+std::vector<int64_t> gemm_skinny_w8_plan_op(int64_t K, int64_t N) {
+  TORCH_CHECK(K >= 1 && N >= 1 && K <= INT32_MAX && N <= INT32_MAX, "pz::gemm_skinny_w8_plan: K and N must be positive ints");
+  return plan_triple(pz::skinny_w8_plan(static_cast<int>(K), static_cast<int>(N)));
+}
+
 // ------------------------------------------------------------------------------ elementwise
 void stage_fwd_op(const Tensor& x, const Tensor& y, at::IntArrayRef ei, at::ArrayRef<double> ef) {
   check_dev(x, "x");
@@ -1454,6 +1469,8 @@ TORCH_LIBRARY(pz, m) {
   m.def("gemm_skinny_eligible(Tensor x, Tensor w, Tensor out) -> bool");
   m.def("gemm_skinny_w8(Tensor x, Tensor w8, Tensor scale, Tensor(a!) out, Tensor? bias, int act) -> ()");
   m.def("gemm_skinny_w8_eligible(Tensor x, Tensor w8, Tensor scale, Tensor out) -> bool");
+  m.def("gemm_skinny_plan(int K, int N, int dtype) -> int[]");
+  m.def("gemm_skinny_w8_plan(int K, int N) -> int[]");
   m.def("gemm_pair_split(Tensor A0, Tensor B0, Tensor C0, Tensor A1, Tensor B1, Tensor C1, int M0, int N0, int M1, "
         "int N1, int K, int engine=0) -> int");
   m.def("gemm_pair(Tensor A0, Tensor B0, Tensor(a!) C0, Tensor A1, Tensor B1, Tensor(b!) C1, int M0, int N0, int M1, "
@@ -1562,6 +1579,8 @@ TORCH_LIBRARY_IMPL(pz, CompositeExplicitAutograd, m) {
   m.impl("pack_segments", TORCH_FN(pack_segments_op));
   m.impl("repr_double", TORCH_FN(repr_double_op));
   m.impl("gemm_last_kernel", TORCH_FN(gemm_last_kernel_op));
+  m.impl("gemm_skinny_plan", TORCH_FN(gemm_skinny_plan_op));
+  m.impl("gemm_skinny_w8_plan", TORCH_FN(gemm_skinny_w8_plan_op));
   m.impl("scan_json_arrays", TORCH_FN(scan_json_arrays_op));
   m.impl("json_skip_keys", TORCH_FN(json_skip_keys_op));
 }

@@ -220,6 +220,17 @@ def gemm_skinny(x: Tensor, w: Tensor, out: Tensor, *, bias: Tensor | None = None
     return out
 
 
+def gemm_skinny_plan(K: int, N: int, dtype: torch.dtype) -> tuple[int, int, int]:
+    """``(strips, slices, slice_len)`` that :func:`gemm_skinny` runs a ``[K, N]`` weight matrix of
+    ``dtype`` (bf16 / fp32) with, as the launcher's own ``pz::skinny_plan`` reports it (nothing is
+    launched): the grid is ``strips x slices`` workgroups, each summing ``slice_len`` K rows (the
+    last slice whatever is left). Never a function of M."""
+    code = {torch.bfloat16: 0, torch.float32: 1}.get(dtype)
+    if code is None:
+        raise ValueError(f"gemm_skinny_plan: bf16 / fp32 operands only, got {dtype}")
+    return tuple(_ops().gemm_skinny_plan(K, N, code))
+
+
 # --------------------------------------------------------------------------------------------
 # weight-only e4m3 inference: column quantiser and its skinny GEMM
 # --------------------------------------------------------------------------------------------
@@ -304,6 +315,12 @@ def gemm_skinny_w8(x: Tensor, w8: Tensor, scale: Tensor, out: Tensor, *, bias: T
     launched for either."""
     _ops().gemm_skinny_w8(x, w8, scale, out, bias, act)
     return out
+
+
+def gemm_skinny_w8_plan(K: int, N: int) -> tuple[int, int, int]:
+    """``(strips, slices, slice_len)`` that :func:`gemm_skinny_w8` runs a ``[K, N]`` e4m3 matrix with,
+    as the launcher's own ``pz::skinny_w8_plan`` reports it (see :func:`gemm_skinny_plan`)."""
+    return tuple(_ops().gemm_skinny_w8_plan(K, N))
 
 
 def _as_2d(x: Tensor) -> tuple[Tensor, tuple]:
@@ -785,6 +802,7 @@ def tensor_summary(t: Tensor, algo: str | None, bins: int) -> dict:
 
 
 __all__ = ["gemm", "gemm_path", "gemm_last_kernel", "gemm_skinny", "gemm_skinny_eligible", "gemm_skinny_w8", "gemm_skinny_w8_eligible",
+           "gemm_skinny_plan", "gemm_skinny_w8_plan",
            "quantize_cols", "quantize_cols_reference", "dequantize_cols", "linear", "activation", "dropout", "softmax", "cross_entropy", "mse_loss",
            "batchnorm", "embedding", "tensor_summary", "epi_spec", "new_seed", "sample_rows", "sample_rows_reference", "nucleus_args",
            "sample_uniform", "generate_resident", "token_logprob", "token_logprob_reference"]

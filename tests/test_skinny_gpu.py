@@ -113,9 +113,8 @@ def test_strided_views_are_read_and_written_in_place(native_lib):
     assert (of[:, :2] == -7.0).all() and (of[:, 2 + n:] == -7.0).all()
 
 
-@pytest.mark.parametrize("m,k,n", [(16, 4096, 1024), (16, 77, 72)])
-def test_same_call_twice_is_bit_identical_and_rows_do_not_depend_on_the_batch(native_lib, m, k, n):
-    x, w, b = _operands(m, k, n, torch.bfloat16, seed=3)
+def _rows_do_not_depend_on_the_batch(m, k, n, dtype):
+    x, w, b = _operands(m, k, n, dtype, seed=3)
     out = torch.empty(m, n, device=DEV)
     again = torch.empty(m, n, device=DEV)
     PF.gemm_skinny(x, w, out, bias=b, act=PF.ACT_TANH)
@@ -129,6 +128,20 @@ def test_same_call_twice_is_bit_identical_and_rows_do_not_depend_on_the_batch(na
         part = torch.empty(rows, n, device=DEV)
         PF.gemm_skinny(x[:rows], w, part, bias=b, act=PF.ACT_TANH)
         assert torch.equal(part, out[:rows]), rows
+
+
+# (16, 4096, 4096): 512-row slices, so a lane of the narrow buckets sums two batches and one of the
+# 16-row bucket eight; random operands, so the summation order shows
+@pytest.mark.parametrize("m,k,n", [(16, 4096, 1024), (16, 77, 72), (16, 4096, 4096)])
+def test_same_call_twice_is_bit_identical_and_rows_do_not_depend_on_the_batch(native_lib, m, k, n):
+    assert PF.gemm_skinny_plan(k, n, torch.bfloat16)[2] == (512 if n == 4096 else 256)
+    _rows_do_not_depend_on_the_batch(m, k, n, torch.bfloat16)
+
+
+def test_fp32_rows_do_not_depend_on_the_batch_with_512_row_slices(native_lib):
+    m, k, n = 16, 4096, 2048
+    assert PF.gemm_skinny_plan(k, n, torch.float32) == (64, 8, 512)
+    _rows_do_not_depend_on_the_batch(m, k, n, torch.float32)
 
 
 def test_ineligible_operands_are_refused_and_nothing_is_launched(native_lib):

@@ -177,8 +177,11 @@ def test_strided_views_are_read_and_written_in_place(native_lib):
     assert (of[:, :2] == -7.0).all() and (of[:, 2 + n:] == -7.0).all()
 
 
-@pytest.mark.parametrize("m,k,n", [(16, 4096, 1024), (16, 77, 80)])
+# (16, 4096, 8192): 512-row slices, so a lane of the narrow buckets sums two batches and one of the
+# 16-row bucket sixteen, two turns of its ring; random operands, so the summation order shows
+@pytest.mark.parametrize("m,k,n", [(16, 4096, 1024), (16, 77, 80), (16, 4096, 8192)])
 def test_same_call_twice_is_bit_identical_and_rows_do_not_depend_on_the_batch(native_lib, m, k, n):
+    assert PF.gemm_skinny_w8_plan(k, n)[2] == (512 if n == 8192 else 256)
     x, w8, scale, b = _operands(m, k, n, seed=3)
     out = torch.empty(m, n, device=DEV)
     again = torch.empty(m, n, device=DEV)
