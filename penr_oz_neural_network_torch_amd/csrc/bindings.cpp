@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "gemm_dispatch.h"
+#include "gemm_sk_plan.h"
 #include "json_format.h"
 #include "pz_kernels.h"
 
@@ -467,6 +468,23 @@ void gemm_pair_op(const Tensor& A0, const Tensor& B0, const Tensor& C0, const Te
     return;
   }
   launch_pair(a, b, A0);
+}
+
+// (grid, sk_tiles, iters, tiles) of the schedule the persistent stream-K engine runs an [M, N] GEMM of
+// depth K with on a budget of `cus` CUs (0 = every CU), an [M1, N1] GEMM of the same K sharing the
+// launch when M1 > 0: what pz::sk_plan returns on this device, nothing launched. Tiles [0, sk_tiles)
+// are cut along K over all `grid` workgroups, the others run whole.
+std::vector<int64_t> gemm_sk_plan_op(int64_t M, int64_t N, int64_t K, int64_t cus, int64_t M1, int64_t N1) {
+  auto whole = [](int64_t v) { return v > 0 && v <= INT32_MAX && v % pz::kSkTile == 0; };
+  TORCH_CHECK(whole(M) && whole(N) && ((M1 == 0 && N1 == 0) || (whole(M1) && whole(N1))),
+              "pz::gemm_sk_plan: whole 256 x 256 tiles only");
+  TORCH_CHECK(K >= 2 * pz::kSkStep && K <= INT32_MAX && K % pz::kSkStep == 0, "pz::gemm_sk_plan: K must be >= 2 steps of 64");
+  TORCH_CHECK(cus >= 0 && cus <= 0xFFFF, "pz::gemm_sk_plan: the CU budget must fit 16 bits");
+  const int64_t t0 = (M / pz::kSkTile) * (N / pz::kSkTile), t1 = (M1 / pz::kSkTile) * (N1 / pz::kSkTile);
+  TORCH_CHECK(t0 + t1 <= INT32_MAX, "pz::gemm_sk_plan: too many tiles");
+  const pz::SkSched s = pz::sk_plan(static_cast<int>(t0), static_cast<int>(t1), static_cast<int>(K), static_cast<int>(cus),
+                                    pz::sk_device_cus());
+  return {s.grid, s.sk_tiles, s.iters, s.tiles};
 }
 
 int64_t gemm_path_op(const Tensor& A, bool a_kc, const Tensor& B, bool b_kc, const Tensor& C, int64_t M, int64_t N,
@@ -1471,6 +1489,7 @@ TORCH_LIBRARY(pz, m) {
   m.def("gemm_skinny_w8_eligible(Tensor x, Tensor w8, Tensor scale, Tensor out) -> bool");
   m.def("gemm_skinny_plan(int K, int N, int dtype) -> int[]");
   m.def("gemm_skinny_w8_plan(int K, int N) -> int[]");
+  m.def("gemm_sk_plan(int M, int N, int K, int cus, int M1=0, int N1=0) -> int[]");
   m.def("gemm_pair_split(Tensor A0, Tensor B0, Tensor C0, Tensor A1, Tensor B1, Tensor C1, int M0, int N0, int M1, "
         "int N1, int K, int engine=0) -> int");
   m.def("gemm_pair(Tensor A0, Tensor B0, Tensor(a!) C0, Tensor A1, Tensor B1, Tensor(b!) C1, int M0, int N0, int M1, "
@@ -1581,6 +1600,7 @@ TORCH_LIBRARY_IMPL(pz, CompositeExplicitAutograd, m) {
   m.impl("gemm_last_kernel", TORCH_FN(gemm_last_kernel_op));
   m.impl("gemm_skinny_plan", TORCH_FN(gemm_skinny_plan_op));
   m.impl("gemm_skinny_w8_plan", TORCH_FN(gemm_skinny_w8_plan_op));
+  m.impl("gemm_sk_plan", TORCH_FN(gemm_sk_plan_op));
   m.impl("scan_json_arrays", TORCH_FN(scan_json_arrays_op));
   m.impl("json_skip_keys", TORCH_FN(json_skip_keys_op));
 }

@@ -98,9 +98,38 @@ inline int epi_kind(const GemmArgs& p) {
   return EK_ANY;
 }
 
-// the stream-K engine's epilogue code for arguments of kind ek = epi_kind(p): ek itself, kSkF32
-// for an fp32 C (weight gradients: plain stores only), -1 where the engine has no epilogue
-inline int sk_takes(const GemmArgs& p, int ek) {
+// One row per instantiated stream-K kernel: operand layout, type of C, the engine's epilogue code.
+// gemm_sk.hip instantiates exactly these and launches from this list, and sk_takes answers from it,
+// so a GEMM the engine is chosen for has a kernel.
+struct SkKey {
+  int a_kc, b_kc;
+  int out;  // DType of C
+  int ek;   // EK_*, or kSkF32
+};
+inline constexpr SkKey kSk[] = {
+    // forward X · W[in, out]
+    {1, 0, DT_BF16, EK_STORE}, {1, 0, DT_BF16, EK_RELU}, {1, 0, DT_BF16, EK_F_RELU_POST},
+    {1, 0, DT_BF16, EK_F_RELU_PREPOST}, {1, 0, DT_BF16, EK_F_PRE}, {1, 0, DT_BF16, EK_ANY},
+    // dX = dZ · Wᵀ
+    {1, 1, DT_BF16, EK_STORE}, {1, 1, DT_BF16, EK_BWD_MASK}, {1, 1, DT_BF16, EK_ANY},
+    // dW = Xᵀ · dZ
+    {0, 0, DT_BF16, EK_STORE}, {0, 0, DT_F32, kSkF32},
+};
+constexpr int kNumSk = sizeof(kSk) / sizeof(kSk[0]);
+
+// the row of kSk that is the kernel of epilogue code ek for p's layout and output type; -1: none
+inline int sk_row(const GemmArgs& p, int ek) {
+  for (int i = 0; i < kNumSk; ++i) {
+    const SkKey& k = kSk[i];
+    if (k.a_kc == (p.a_kc != 0) && k.b_kc == (p.b_kc != 0) && k.out == p.out_dtype && k.ek == ek) return i;
+  }
+  return -1;
+}
+
+// the epilogue code the stream-K engine would run arguments of kind ek = epi_kind(p) with: ek
+// itself, kSkF32 for an fp32 C (weight gradients: plain stores only), -1 where its epilogues
+// cannot do what p asks
+inline int sk_epilogue(const GemmArgs& p, int ek) {
   if (p.out_dtype == DT_F32)
     return (p.epi_mode != EPI_STORE || p.mask != nullptr || p.out8 != nullptr || p.colsum != nullptr) ? -1 : kSkF32;
   if (p.out_dtype != DT_BF16 || p.accumulate) return -1;
@@ -110,6 +139,13 @@ inline int sk_takes(const GemmArgs& p, int ek) {
   if (p.mask != nullptr) return p.epi.act == ACT_RELU ? ek : -1;
   if (p.aux == nullptr || p.aux_dtype != DT_BF16 || p.ldaux % 8 != 0 || !aligned16(p.aux)) return -1;
   return ek;
+}
+
+// the stream-K engine's epilogue code for p, -1 where it has no kernel of that code in p's layout
+// (kSk): those GEMMs stay on the tiled kernels
+inline int sk_takes(const GemmArgs& p, int ek) {
+  const int code = sk_epilogue(p, ek);
+  return code >= 0 && sk_row(p, code) >= 0 ? code : -1;
 }
 
 // ------------------------------------------------------------------------------------ eligibility

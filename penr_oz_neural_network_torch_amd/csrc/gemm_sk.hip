@@ -33,11 +33,14 @@
 //  * Two problems of one layout / epilogue kind / K may share a launch (the two skinny weight-
 //    gradient GEMMs of a 3-layer MLP): their tiles form one schedule.
 #include <algorithm>
+#include <array>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #include "pz_common.h"
 #include "gemm_dispatch.h"
+#include "gemm_sk_plan.h"
 
 namespace pz {
 namespace {
@@ -65,7 +68,7 @@ constexpr int kSkStampUnits = 6;
 #define PZ_SK_NOTE(u, v) do {} while (0)
 #endif
 
-constexpr int kSkB = 256;                    // macro tile BM = BN
+constexpr int kSkB = kSkTile;                // macro tile BM = BN (gemm_sk_plan.h)
 constexpr int kSkSlab = kSkB * kSkB;         // fp32 floats of one partial tile
 constexpr int kSkLds = 128 * 1024;           // both main loops' rings = the epilogue's C image
 
@@ -82,16 +85,7 @@ template <int W> struct SkGeo {
 };
 
 static_assert(kSkB == 256 && SkGeo<8>::BK == 64, "sk_eligible (gemm_dispatch.h) states the tile and the K step");
-
-struct SkSched {
-  int nprob;
-  int tiles0;           // tiles of problem 0 (problem 1's tiles follow)
-  int tiles;            // all tiles
-  int iters;            // K steps per tile
-  int grid;             // workgroups
-  int sk_tiles;         // tiles [0, sk_tiles) are stream-K'd over every workgroup
-  long long sk_iters;   // sk_tiles * iters
-};
+static_assert(SkGeo<8>::BK == kSkStep, "gemm_sk_plan.h plans in the main loop's K steps");
 
 struct SkArgs {
   GemmArgs p[2];
@@ -99,17 +93,6 @@ struct SkArgs {
   float* ws;      // [2 * grid][256 * 256] partial slabs: slab 2w = workgroup w's first unit, 2w+1 its last
   int* counters;  // [sk_tiles] tickets, zero between launches (the last arriver resets its tile's)
 };
-
-// first stream-K iteration of workgroup w (w = grid: the end)
-PZ_DEV long long sk_start(const SkSched& s, int w) { return static_cast<long long>(w) * s.sk_iters / s.grid; }
-
-// the workgroup whose stream-K range holds iteration `it`
-PZ_DEV int sk_owner(const SkSched& s, long long it) {
-  int w = static_cast<int>(it * s.grid / s.sk_iters);
-  while (w + 1 < s.grid && sk_start(s, w + 1) <= it) ++w;
-  while (w > 0 && sk_start(s, w) > it) --w;
-  return w;
-}
 
 PZ_DEV void sk_barrier() {
   __builtin_amdgcn_sched_barrier(0);
@@ -286,37 +269,21 @@ gemm_sk_kernel(const SkArgs g) {
   const int wm = wave / G::WN, wn = wave % G::WN;
 
   // Work units in schedule order: the stream-K range [s0, s1) cut at tile boundaries, then the
-  // data-parallel tiles w, w + grid, ... ONE loop, so the unit body is inlined once.
-  const long long s0 = s.sk_iters > 0 ? sk_start(s, w) : 0, s1 = s.sk_iters > 0 ? sk_start(s, w + 1) : 0;
-  long long it = s0;
-  int dp_t = s.sk_tiles + w;
+  // data-parallel tiles w, w + grid, ... (gemm_sk_plan.h: sk_walk / sk_next). ONE loop, so the
+  // unit body is inlined once.
+  SkWalk walk = sk_walk(s, w);
   int unit = 0;  // (diagnostic stamps only)
   (void)unit;
   for (;;) {
     // this unit: K steps [kb, ke) of tile t; slab >= 0: a stream-K partial tile
-    int t, kb, ke, slab;
-    if (it < s1) {
-      t = static_cast<int>(it / s.iters);
-      kb = static_cast<int>(it - static_cast<long long>(t) * s.iters);
-      const long long left = s1 - it;
-      ke = left < static_cast<long long>(s.iters - kb) ? kb + static_cast<int>(left) : s.iters;
-      slab = (kb == 0 && ke == s.iters) ? -1 : 2 * w + (it == s0 ? 0 : 1);
-      it += ke - kb;
-    } else if (dp_t < s.tiles) {
-      t = dp_t;
-      kb = 0;
-      ke = s.iters;
-      slab = -1;
-      dp_t += s.grid;
-    } else {
-      break;
-    }
+    const SkUnit u = sk_next(s, w, walk);
+    if (u.t < 0) break;
     // (64-bit divisions run on the VALU: pin the unit's scalars to SGPRs, or every buffer
     // descriptor / soffset built from them becomes a waterfall loop)
-    t = __builtin_amdgcn_readfirstlane(t);
-    kb = __builtin_amdgcn_readfirstlane(kb);
-    ke = __builtin_amdgcn_readfirstlane(ke);
-    slab = __builtin_amdgcn_readfirstlane(slab);
+    const int t = __builtin_amdgcn_readfirstlane(u.t);
+    const int kb = __builtin_amdgcn_readfirstlane(u.kb);
+    const int ke = __builtin_amdgcn_readfirstlane(u.ke);
+    const int slab = __builtin_amdgcn_readfirstlane(u.slab);
     PZ_SK_STAMP(unit, 0);
     PZ_SK_NOTE(unit, (static_cast<uint64_t>(t) << 40) | (static_cast<uint64_t>(kb) << 20) | static_cast<uint64_t>(ke) |
                          (slab >= 0 ? (uint64_t(1) << 63) : 0));
@@ -357,9 +324,10 @@ gemm_sk_kernel(const SkArgs g) {
       });
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      const long long t0 = static_cast<long long>(t) * s.iters;
-      const int wlo = __builtin_amdgcn_readfirstlane(sk_owner(s, t0));
-      const int whi = __builtin_amdgcn_readfirstlane(sk_owner(s, t0 + s.iters - 1));
+      const long long t0 = sk_tile_start(s, t);
+      const SkPair who = sk_contributors(s, t0);
+      const int wlo = __builtin_amdgcn_readfirstlane(who.wlo);
+      const int whi = __builtin_amdgcn_readfirstlane(who.whi);
       PZ_LDS int* flag = (PZ_LDS int*)(smem);
       if (tid == 0) {
         const int prev = __hip_atomic_fetch_add(g.counters + t, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -373,7 +341,7 @@ gemm_sk_kernel(const SkArgs g) {
         ++unit;
         continue;
       }
-      auto slab_of = [&](int c) { return __builtin_amdgcn_readfirstlane(2 * c + (sk_start(s, c) < t0 ? 1 : 0)); };
+      auto slab_of = [&](int c) { return __builtin_amdgcn_readfirstlane(sk_slab_of(s, c, t0)); };
       auto rs_of = [&](int c) {
         return __builtin_amdgcn_make_buffer_rsrc(g.ws + static_cast<int64_t>(slab_of(c)) * kSkSlab, 0, kSkSlab * 4,
                                                  0x00020000);
@@ -426,28 +394,10 @@ int device_cus() {
   return n;
 }
 
+// the schedule of probs[0 .. n) on this device (gemm_sk_plan.h)
 SkSched sk_plan(const GemmArgs* probs, int n) {
-  SkSched s{};
-  s.nprob = n;
-  s.tiles0 = (probs[0].M / kSkB) * (probs[0].N / kSkB);
-  s.tiles = s.tiles0 + (n > 1 ? (probs[1].M / kSkB) * (probs[1].N / kSkB) : 0);
-  constexpr int bk = SkGeo<8>::BK;
-  s.iters = probs[0].K / bk;
-  const int cus = device_cus();
-  int grid = probs[0].cus > 0 ? std::min(probs[0].cus, cus) : cus;
-  const int T = s.tiles;
-  // At most TWO contributors per tile. Fewer tiles than workgroups: each tile in two K halves on
-  // 2T workgroups when the budget holds them and the halves are >= 256 deep, else one workgroup
-  // per tile (data-parallel; the other CUs idle but the survivors run faster per step). At least
-  // as many tiles: the "two-tile" region gives every workgroup >= one tile of K steps, so a tile
-  // meets at most two workgroups' ranges.
-  if (T < grid) grid = (2 * T <= grid && s.iters * bk >= 512) ? 2 * T : T;
-  int sk = 0;
-  if (T % grid != 0) sk = T < grid ? T : T % grid + grid;
-  s.grid = grid;
-  s.sk_tiles = sk;
-  s.sk_iters = static_cast<long long>(sk) * s.iters;
-  return s;
+  auto tiles_of = [](const GemmArgs& p) { return (p.M / kSkB) * (p.N / kSkB); };
+  return pz::sk_plan(tiles_of(probs[0]), n > 1 ? tiles_of(probs[1]) : 0, probs[0].K, probs[0].cus, device_cus());
 }
 
 template <bool AKC, bool BKC, typename OutT, int EK, int W>
@@ -456,38 +406,24 @@ hipError_t sk_launch(const SkArgs& a, hipStream_t st) {
                                                             {"sk", 0, kSkB, kSkB, EK, 1});
 }
 
+// The launchers of gemm_dispatch.h's kSk, row by row: every stream-K kernel the library holds
+using SkLauncher = hipError_t (*)(const SkArgs&, hipStream_t);
+template <size_t... I>
+constexpr std::array<SkLauncher, sizeof...(I)> sk_launchers(std::index_sequence<I...>) {
+  return {{&sk_launch<kSk[I].a_kc != 0, kSk[I].b_kc != 0, std::conditional_t<kSk[I].out == DT_BF16, uint16_t, float>,
+                      kSk[I].ek, 8>...}};
+}
+constexpr auto kSkLaunchers = sk_launchers(std::make_index_sequence<kNumSk>{});
+
+// launch the kernel of epilogue code ek (sk_takes) for a.p[0]'s layout and output type
 hipError_t sk_dispatch(const SkArgs& a, int ek, hipStream_t st) {
-  const GemmArgs& p = a.p[0];
-  if (p.a_kc && !p.b_kc) {  // forward X · W[in, out]
-    switch (ek) {
-      case EK_STORE: return sk_launch<true, false, uint16_t, EK_STORE, 8>(a, st);
-      case EK_RELU: return sk_launch<true, false, uint16_t, EK_RELU, 8>(a, st);
-      case EK_F_RELU_POST: return sk_launch<true, false, uint16_t, EK_F_RELU_POST, 8>(a, st);
-      case EK_F_RELU_PREPOST: return sk_launch<true, false, uint16_t, EK_F_RELU_PREPOST, 8>(a, st);
-      case EK_F_PRE: return sk_launch<true, false, uint16_t, EK_F_PRE, 8>(a, st);
-      case EK_ANY: return sk_launch<true, false, uint16_t, EK_ANY, 8>(a, st);
-      default: return hipErrorInvalidValue;
-    }
-  }
-  if (p.a_kc && p.b_kc) {  // dX = dZ · Wᵀ
-    switch (ek) {
-      case EK_STORE: return sk_launch<true, true, uint16_t, EK_STORE, 8>(a, st);
-      case EK_BWD_MASK: return sk_launch<true, true, uint16_t, EK_BWD_MASK, 8>(a, st);
-      case EK_ANY: return sk_launch<true, true, uint16_t, EK_ANY, 8>(a, st);
-      default: return hipErrorInvalidValue;
-    }
-  }
-  if (!p.a_kc && !p.b_kc) {  // dW = Xᵀ · dZ
-    switch (ek) {
-      case EK_STORE: return sk_launch<false, false, uint16_t, EK_STORE, 8>(a, st);
-      case kSkF32: return sk_launch<false, false, float, kSkF32, 8>(a, st);
-      default: return hipErrorInvalidValue;
-    }
-  }
-  return hipErrorInvalidValue;
+  const int row = sk_row(a.p[0], ek);
+  return row < 0 ? hipErrorInvalidValue : kSkLaunchers[row](a, st);
 }
 
 }  // namespace
+
+int sk_device_cus() { return device_cus(); }
 
 int sk_tickets(const GemmArgs* probs, int n) { return sk_plan(probs, n).sk_tiles; }
 

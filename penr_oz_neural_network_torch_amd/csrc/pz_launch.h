@@ -126,6 +126,7 @@ struct GemmArgs {
 bool sk_eligible(const GemmArgs& p);
 int64_t sk_ws_floats(const GemmArgs* probs, int n);
 int sk_tickets(const GemmArgs* probs, int n);  // per-tile ticket counters needed
+int sk_device_cus();  // the CU count the engine plans with (gemm_sk_plan.h sk_plan's device_cus)
 hipError_t gemm_sk(const GemmArgs* probs, int n, float* ws, int* counters, hipStream_t stream);
 bool sk_default();  // PZ_GEMM_SK: the engine gemm() picks for eligible shapes
 // PZ_DETERMINISTIC (default 1): bias-gradient column sums of the bf16 GEMM epilogues and heads are

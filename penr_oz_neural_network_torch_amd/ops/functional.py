@@ -145,6 +145,16 @@ def gemm_pair_split(a0: Tensor, b0: Tensor, out0: Tensor, a1: Tensor, b1: Tensor
                                       out1.shape[1], a0.shape[0], engine))
 
 
+def gemm_sk_plan(M: int, N: int, K: int, cus: int = 0, M1: int = 0, N1: int = 0) -> tuple[int, int, int, int]:
+    """``(grid, sk_tiles, iters, tiles)`` of the schedule the persistent stream-K engine (``engine=2``)
+    runs an ``[M, N]`` GEMM of depth ``K`` with on a budget of ``cus`` CUs (0 = every CU), as the
+    launcher's own ``pz::sk_plan`` reports it on this device (nothing is launched); ``M1, N1``: a
+    second problem of the same ``K`` sharing the launch (:func:`gemm_pair`). ``grid`` workgroups walk
+    ``tiles`` 256 x 256 tiles of ``iters`` 64-deep K steps; tiles ``[0, sk_tiles)`` are cut along K over
+    all workgroups (at most two contributors each), the others run whole, ``grid`` at a time."""
+    return tuple(_ops().gemm_sk_plan(M, N, K, cus, M1, N1))
+
+
 def relu_mask_shape(m: int, n: int) -> tuple[int, int]:
     """Shape of the tile-blocked ReLU bitmask of an ``[m, n]`` output (csrc/pz_launch.h
     GemmArgs::mask): 256 x 256 element blocks of 8 KiB (256 rows of 32 B) in block-row-major order,
@@ -802,7 +812,7 @@ def tensor_summary(t: Tensor, algo: str | None, bins: int) -> dict:
 
 
 __all__ = ["gemm", "gemm_path", "gemm_last_kernel", "gemm_skinny", "gemm_skinny_eligible", "gemm_skinny_w8", "gemm_skinny_w8_eligible",
-           "gemm_skinny_plan", "gemm_skinny_w8_plan",
+           "gemm_skinny_plan", "gemm_skinny_w8_plan", "gemm_sk_plan",
            "quantize_cols", "quantize_cols_reference", "dequantize_cols", "linear", "activation", "dropout", "softmax", "cross_entropy", "mse_loss",
            "batchnorm", "embedding", "tensor_summary", "epi_spec", "new_seed", "sample_rows", "sample_rows_reference", "nucleus_args",
            "sample_uniform", "generate_resident", "token_logprob", "token_logprob_reference"]

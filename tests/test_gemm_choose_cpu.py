@@ -5,9 +5,14 @@ checked without a GPU.
 and run once on every case below: GemmArgs of the shape, layout, types, epilogue and flags that the GPU
 tests' run_case / run_pair / launch_update hand to the binding (contiguous operands), the split planned
 as the binding plans it. The kernel it names must be the one the GPU test modules predict with their own
-restatements of the dispatch (``expected_kernel``, ``PAIR_KERNEL``, ``UPDATE_KERNEL``: imported here, not
-copied), i.e. the one they assert through ``gemm_last_kernel()`` on the device, and every tiled, w4 and
-pair choice must have a row in the table the launchers are built from.
+restatements of the dispatch (``expected_kernel``, ``PAIR_KERNEL``, ``UPDATE_KERNEL``, ``sk_kernel``: imported
+here, not copied), i.e. the one they assert through ``gemm_last_kernel()`` on the device, and every tiled, w4
+and pair choice must have a row in the table the launchers are built from.
+
+The stream-K engine's table (kSk): every form of FORMS in each of the four operand layouts, asked for
+by engine 2, by engine 0 with PZ_GEMM_SK and by engine 0 with a CU budget, is chosen for the engine
+exactly where test_gemm_sk_exact_gpu.SK_TABLE (the restatement its form list comes from) has the
+(layout, kind) pair, and is a tiled or generic kernel everywhere else.
 """
 import os
 import shutil
@@ -20,6 +25,7 @@ from penr_oz_neural_network_torch_amd.ops import functional as PF
 from tests import test_gemm_exact_gpu as EX
 from tests import test_gemm_fp8_exact_gpu as F8
 from tests import test_gemm_pair_update_gpu as PU
+from tests import test_gemm_sk_exact_gpu as SKX
 from tests.helpers import PAIR_SPLIT_CASES, gemm_pair_split_plan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,10 +106,24 @@ def cases():
     for layout in ("fwd", "dw", "dx"):   # test_gemm_wide_gpu.py::test_gemm_fp32_matrix_cores
         out.append((gemm_line((640, 320, 1024), "plain", layout=layout, in_dtype=torch.float32, out_dtype=torch.float32,
                               engine=0), "wide/var0/128x128/ek0/split1"))
-    for form, kind in EX.SK_KIND.items():
+    for form in SKX.SK_FORMS:
+        assert form not in EX.SK_KIND or SKX.sk_kernel(form) == f"sk/var0/256x256/ek{EX.SK_KIND[form]}/split1"
         for p in EX.FORMS[form].p:
             for cus in (37, 200):
-                out.append((gemm_line(EX.SK, form, p, engine=2, cus=cus), f"sk/var0/256x256/ek{kind}/split1"))
+                out.append((gemm_line(EX.SK, form, p, engine=2, cus=cus), SKX.sk_kernel(form)))
+    return out
+
+
+def sk_table_cases():
+    """(input line, the stream-K kernel's name or None) of every form in every layout, and of the pairs
+    outside the table at a second shape, each asked for in the three ways that reach the engine."""
+    pairs = [(SKX.SCHEDULES["twotile"][0], form, layout) for form in EX.FORMS for layout in EX.LAYOUTS]
+    pairs += [(SKX.SCHEDULES[s][0], form, layout) for s in ("twotile", "sk_dp") for form, layout in SKX.OUTSIDE]
+    out = []
+    for shape, form, layout in pairs:
+        for p in EX.FORMS[form].p:
+            for kw in (dict(engine=2), dict(engine=0, sk=1), dict(engine=0, cus=37)):
+                out.append((gemm_line(shape, form, p, layout=layout, **kw), SKX.sk_kernel(form, layout)))
     return out
 
 
@@ -161,4 +181,24 @@ def test_every_case_chooses_the_kernel_the_gpu_tests_assert(chooser):
     # the cells the issue names
     assert F8.expected_kernel("v15", F8.SW4SHORT, "plain") == "mfma/var15/256x256/ek0/split1" in names
     assert {f"mfma/var14/256x256/ek1/split{s}" for s in (1, 4, 8)} <= names
-    assert {f"sk/var0/256x256/ek{k}/split1" for k in (1, 3, 4, 5, 6, 100)} <= names
+    assert {f"sk/var0/256x256/ek{k}/split1" for k in (0, 1, 2, 3, 4, 5, 6, 100)} <= names
+
+
+def test_the_stream_k_engine_is_chosen_exactly_where_it_has_a_kernel(chooser):
+    table = sk_table_cases()
+    got = chooser([line for line, _ in table])
+    assert len(got) == len(table)
+    wrong = []
+    for (line, want), g in zip(table, got):
+        name, _, row = g.partition(" ")
+        family = name.split("/")[0]
+        if want is not None:
+            if name != want:
+                wrong.append((line, g, want))
+        elif family not in ("mfma", "w4", "generic") or (family != "generic" and row != "row"):
+            wrong.append((line, g, "a tiled kernel with a row, or the generic one"))
+    assert not wrong, wrong[:10]
+    print(f"{len(table)} cases, {sum(w is not None for _, w in table)} on the engine")
+    # the pairs gemm_choose used to hand the engine although it has no kernel for them
+    for form, layout in SKX.OUTSIDE:
+        assert SKX.sk_kernel(form, layout) is None and SKX.sk_kernel(form) is not None

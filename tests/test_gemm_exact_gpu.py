@@ -33,7 +33,10 @@ Dispatch cells reached (kFill = 240):
                                     fp64 operands with fp64 C, bias, aux and column sums there and at (9, 9, 9)
                                     (fp64 bounds: run_case; the fp32 / fp64 matrix-core kernel runs through
                                     run_case from test_gemm_wide_exact_gpu.py)
-  sk/var0/256x256/ek1|3|4|5|6|100    (1536, 1280, 512) on 37 CUs (30 data-parallel tiles) and 200 (two K halves)
+  sk/var0/256x256/ek1|3|4|5|6|100    (1536, 1280, 512) on 37 CUs (30 data-parallel tiles) and 200 (two K halves);
+                                    every schedule shape of the engine (two-tile regions, data-parallel rounds,
+                                    uneven cuts, pairs) and every epilogue it has, ek0 and ek2 among them:
+                                    test_gemm_sk_exact_gpu.py
 Not reached on purpose: the !buffer_addressable fallbacks (VAR 0; need a 4 GiB operand), fp32 outputs of the
 stream-K engine outside the dW layout (it has none). fp8 operands run through this file's run_case
 from test_gemm_fp8_exact_gpu.py (its ``fmts`` / ``layout`` / ``q8`` arguments); gemm_pair and
@@ -320,12 +323,13 @@ F64_BWD_ACT_ULPS = 16.0
 
 def run_case(shape, form, p=0.5, *, engine=1, cus=0, force_generic=False, no_split=False, strided=False,
              idx_ld=0, in_dtype=BF16, out_dtype=None, store_c=True, layout=None, fmts=None, q8="std",
-             bias_dtype=F32, colsum_dtype=F32, aux_dtype=None, hi=4, pad=None, odd=0):
+             bias_dtype=F32, colsum_dtype=F32, aux_dtype=None, hi=4, pad=None, odd=0, alpha=None):
     """One GEMM launch of ``form`` checked against the fp64 reference. Returns what it produced.
     ``fmts`` = (format of A, format of B): fp8 operands in layout ``layout`` (default: the form's),
     dequantised by F8_SCALES (folded into the reference's alpha; the kernel's alpha is raised by as
     much, so that every form sees the values the bf16 run sees). ``q8``: which OUT8_Q factor the
-    fp8 copy takes ("std": 2^-3, at which e4m3 saturates too).
+    fp8 copy takes ("std": 2^-3, at which e4m3 saturates too). ``alpha``: a power of two instead of
+    alpha_of's (whose e4m3 saturation is sized for K <= 192 and K = 4096).
 
     ``in_dtype`` fp32 / fp64 (gemm_wide.hip, gemm_generic.hip): ``hi`` = the operands' integer range
     (they are generated in ``in_dtype``), ``bias_dtype`` / ``colsum_dtype`` fp32 or fp64,
@@ -360,7 +364,7 @@ def run_case(shape, form, p=0.5, *, engine=1, cus=0, force_generic=False, no_spl
     what = f"{form} {shape} p={p}"
     if in_dtype != BF16:
         what += f" {str(in_dtype)[6:]}->{str(out_dtype)[6:]}" + (" generic" if force_generic else "")
-    alpha = alpha_of(f, K)
+    alpha = alpha_of(f, K) if alpha is None else alpha
     k_alpha, scales = alpha, {}
     if fmts is not None:
         k_alpha = alpha / (F8_SCALES[0] * F8_SCALES[1])
