@@ -150,6 +150,19 @@ class GenerateRequest(ModelRequest):
                                                     "returned token under the model's own distribution (temperature 1, "
                                                     "no top-k / top-p / min-p truncation), from one scoring pass after "
                                                     "the loop. Omitted: nothing extra is computed.")
+    top_logprobs: int | None = Field(None, description="k in [1, min(classes, 64)]: the response gains 'top_tokens' and "
+                                                       "'top_logprobs', for every returned token the k classes the model "
+                                                       "found most likely at its position, most likely first, and their "
+                                                       "log-probabilities, from the same scoring pass as logprobs. "
+                                                       "Omitted: nothing extra is computed.")
+
+
+class ClassifyRequest(ModelRequest):
+    inputs: list = Field(..., description="One input vector (1D) or a batch of them (2D); id sequences for "
+                                          "embedding models. The model must end in a softmax layer.")
+    top_k: int = Field(1, description="How many of the most likely classes to return per row, in [1, min(classes, 64)], "
+                                      "most likely first; equally likely classes in ascending order.")
+    weights: str | None = Field(None, description="'fp8': weight-only e4m3 copies, as on /predict/.")
 
 
 class ScoreRequest(ModelRequest):
@@ -159,6 +172,11 @@ class ScoreRequest(ModelRequest):
     pad_token: int = Field(0, description="Id that left-pads every row, as on /generate/.")
     weights: str | None = Field(None, description="'fp8': weight-only e4m3 copies, as on /predict/.")
     details: bool = Field(True, description="false: only tokens, nll, perplexity and top1 come back, no per-id lists.")
+    top_logprobs: int | None = Field(None, description="k in [1, min(classes, 64)]: the response gains 'top_tokens' and "
+                                                       "'top_logprobs', for every scored id the k classes the model found "
+                                                       "most likely there, most likely first, and their log-probabilities "
+                                                       "(needs details; rows x longest row x k at most 16,777,216). "
+                                                       "Omitted: nothing extra is computed.")
 
 
 class TrainingRequest(ModelRequest):
@@ -318,6 +336,29 @@ def predict_model_output(body: PredictRequest = Body(..., openapi_examples=PREDI
         raise ValueError(str(e))
 
 
+CLASSIFY_EXAMPLES = {
+    "single": {"summary": "One vector", "description": "One 9-cell board of a softmax-head model; the three most likely "
+                                                       "moves and their probabilities.",
+               "value": {"model_id": "test", "inputs": EXAMPLES[2]["activation_vector"], "top_k": 3}},
+    "batch": {"summary": "A batch", "description": "Three boards in one request; the most likely move of each.",
+              "value": {"model_id": "test", "inputs": [ex["activation_vector"] for ex in EXAMPLES[:3]]}},
+}
+
+
+@app.post("/classify/")
+def classify_inputs(body: ClassifyRequest = Body(..., openapi_examples=CLASSIFY_EXAMPLES)):
+    model_id = body.model_id
+    log.info(f"Requesting classification for model {model_id}")
+    model = _cached_model(model_id)
+    _check_predict_inputs(model, body.inputs)
+    try:
+        if body.weights is None:
+            return model.classify(body.inputs, top_k=body.top_k)
+        return model.classify(body.inputs, top_k=body.top_k, weights=body.weights)
+    except IndexError as e:  # an embedding id outside the vocabulary is a bad request
+        raise ValueError(str(e))
+
+
 GENERATE_EXAMPLES = {
     "single": {"summary": "One context", "description": "Ten tokens after one context of a character model "
                                                         "(vocabulary 27, id 0 ends a word).",
@@ -336,7 +377,8 @@ def generate_tokens(body: GenerateRequest = Body(..., openapi_examples=GENERATE_
     model = _cached_model(model_id)
     # (only when asked for, as weights on /predict/)
     extra = {**({} if body.loop is None else {"loop": body.loop}), **nucleus_args(body.top_p, body.min_p),
-             **({} if body.logprobs is None else {"logprobs": body.logprobs})}
+             **({} if body.logprobs is None else {"logprobs": body.logprobs}),
+             **({} if body.top_logprobs is None else {"top_logprobs": body.top_logprobs})}
     try:
         return model.generate(body.context, body.max_new_tokens, temperature=body.temperature, top_k=body.top_k,
                               seed=body.seed, stop_token=body.stop_token, pad_token=body.pad_token, weights=body.weights,
@@ -367,7 +409,8 @@ def score_sequences(body: ScoreRequest = Body(..., openapi_examples=SCORE_EXAMPL
         raise ValueError(f"a request scores at most {SCORE_MAX_IDS} ids")
     model = _cached_model(model_id)
     try:
-        return model.score(body.sequences, pad_token=body.pad_token, weights=body.weights, details=body.details)
+        extra = {} if body.top_logprobs is None else {"top_logprobs": body.top_logprobs}  # (only when asked for)
+        return model.score(body.sequences, pad_token=body.pad_token, weights=body.weights, details=body.details, **extra)
     except IndexError as e:  # an id that is no class of the model is a bad request
         raise ValueError(str(e))
 

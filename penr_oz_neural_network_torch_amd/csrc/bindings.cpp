@@ -822,6 +822,43 @@ void token_logprob_op(const Tensor& logits, const Tensor& targets, const Tensor&
   PZ_HIP_CHECK(pz::token_logprob(a, cur_stream(logits)));
 }
 
+// the k most likely columns of every row of the logits, in rank order, and their log-probabilities (csrc/topk_rows.hip)
+void topk_rows_op(const Tensor& logits, int64_t k, const Tensor& idx, const Tensor& logprob) {
+  const char* who = "pz::topk_rows: ";
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kFloat && logits.dim() == 2, who,
+              "logits must be a GPU fp32 [rows, V] tensor");
+  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == at::kInt && idx.dim() == 2, who, "idx must be a GPU int32 [rows, k] tensor");
+  TORCH_CHECK(logprob.is_cuda() && logprob.scalar_type() == at::kFloat && logprob.dim() == 2, who,
+              "logprob must be a GPU fp32 [rows, k] tensor");
+  const int64_t rows = logits.size(0), cols = logits.size(1);
+  TORCH_CHECK(cols >= 1 && cols <= pz::kSampleMaxCols && rows <= INT32_MAX, who, "shape out of range: [", rows, ", ", cols, "]");
+  TORCH_CHECK(k >= 1 && k <= std::min<int64_t>(cols, pz::kTopkMaxK), who, "k must be in [1, min(V, ", pz::kTopkMaxK,
+              ")] = [1, ", std::min<int64_t>(cols, pz::kTopkMaxK), "], got ", k);
+  TORCH_CHECK(idx.size(0) == rows && idx.size(1) == k && logprob.size(0) == rows && logprob.size(1) == k, who,
+              "idx and logprob must be [", rows, ", ", k, "], got [", idx.size(0), ", ", idx.size(1), "] and [",
+              logprob.size(0), ", ", logprob.size(1), "]");
+  TORCH_CHECK(idx.device() == logits.device() && logprob.device() == logits.device(), who,
+              "every tensor must be on the logits' device");
+  TORCH_CHECK(cols == 1 || logits.stride(1) == 1, who, "logits must have a unit column stride, got ", logits.stride(1));
+  TORCH_CHECK(rows <= 1 || logits.stride(0) >= cols, who, "logits rows overlap: row stride ", logits.stride(0), " < V = ", cols);
+  TORCH_CHECK(k == 1 || (idx.stride(1) == 1 && logprob.stride(1) == 1), who, "idx and logprob must have a unit column stride, got ",
+              idx.stride(1), " and ", logprob.stride(1));
+  TORCH_CHECK(rows <= 1 || (idx.stride(0) >= k && logprob.stride(0) >= k), who, "output rows overlap: row strides ",
+              idx.stride(0), " and ", logprob.stride(0), " < k = ", k);
+  if (rows == 0) return;
+  pz::TopkRowsArgs a{};
+  a.logits = logits.data_ptr<float>();
+  a.ld = logits.stride(0);
+  a.rows = rows;
+  a.cols = static_cast<int>(cols);
+  a.k = static_cast<int>(k);
+  a.idx = idx.data_ptr<int>();
+  a.idx_ld = idx.stride(0);
+  a.logprob = logprob.data_ptr<float>();
+  a.logprob_ld = logprob.stride(0);
+  PZ_HIP_CHECK(pz::topk_rows(a, cur_stream(logits)));
+}
+
 // a whole generation request in one launch (csrc/generate_resident.hip). `plan` is the int list of
 // engine/resident.py: resident_plan. Whatever a wrong plan could turn into a stray LDS or global
 // access is refused here: the kernel trusts every number it is handed.
@@ -1511,6 +1548,7 @@ TORCH_LIBRARY(pz, m) {
         "int top_k, int seed_lo, int seed_hi, int stop_token=-1, int row0=0, Tensor(c!)? logits_out=None, float top_p=1.0, "
         "float min_p=0.0) -> ()");
   m.def("token_logprob(Tensor logits, Tensor targets, Tensor(a!) logprob, Tensor(b!)? rank) -> ()");
+  m.def("topk_rows(Tensor logits, int k, Tensor(a!) idx, Tensor(b!) logprob) -> ()");
   m.def("softmax_bwd(Tensor g, Tensor y, Tensor(a!) dx) -> ()");
   m.def("colsum(Tensor x, Tensor(a!) out) -> ()");
   m.def("gather_rows(Tensor data, Tensor? indices, int seed_lo, int seed_hi, Tensor(a!) out, int rows_valid, "
@@ -1571,6 +1609,7 @@ TORCH_LIBRARY_IMPL(pz, CUDA, m) {
   m.impl("sample_rows", TORCH_FN(sample_rows_op));
   m.impl("generate_resident", TORCH_FN(generate_resident_op));
   m.impl("token_logprob", TORCH_FN(token_logprob_op));
+  m.impl("topk_rows", TORCH_FN(topk_rows_op));
   m.impl("softmax_bwd", TORCH_FN(softmax_bwd_op));
   m.impl("colsum", TORCH_FN(colsum_op));
   m.impl("gather_rows", TORCH_FN(gather_rows_op));

@@ -143,6 +143,22 @@ struct TokenLogprobArgs {
 };
 hipError_t token_logprob(const TokenLogprobArgs& a, hipStream_t s);
 
+// per row of fp32 logits, the k columns of rank 0 .. k - 1 (token_logprob's rank) in that order and their
+// log-probabilities (topk_rows.hip): classify(), top_logprobs. Strides in elements.
+constexpr int kTopkMaxK = 64;
+struct TopkRowsArgs {
+  const float* logits;  // [rows][ld], ld >= cols, unit column stride
+  int64_t ld;
+  int64_t rows;
+  int cols;
+  int k;                // 1 <= k <= min(cols, kTopkMaxK)
+  int* idx;             // [rows][idx_ld], idx_ld >= k: descending logit, then ascending column
+  int64_t idx_ld;
+  float* logprob;       // [rows][logprob_ld], logprob_ld >= k: the bits token_logprob gives idx[r][j]
+  int64_t logprob_ld;
+};
+hipError_t topk_rows(const TopkRowsArgs& a, hipStream_t s);
+
 // one-launch token generation with the whole model in LDS (generate_resident.hip). The plan is
 // engine/resident.py's int list: kResHead header ints, kResParam per parameter, kResStage per stage.
 constexpr int kResMaxStages = 16, kResMaxParams = 64, kResMaxSteps = 4096;

@@ -75,6 +75,10 @@ finds ids it is given. ``seq [R, W]`` is uploaded and range-checked once; every 
 ``PF.token_logprob`` launch per chunk (csrc/token_logprob.hip) writes the log-probability and the rank
 of ``seq[r, L + j]`` straight into the ``[R, W - L]`` results, which stay on the device. It is also what
 ``generate(..., logprobs=True)`` runs once, after its loop, on ``[context | tokens]``.
+
+Top-k answers (csrc/topk_rows.hip): :meth:`FusedPredictor.classify` is ``_logits`` and one ``PF.topk_rows``
+launch — the k most likely classes of every row in rank order with their log-probabilities, no softmax
+row; ``score(..., top_logprobs=k)`` makes the same launch once more per chunk on the chunk's logits.
 """
 from __future__ import annotations
 
@@ -256,6 +260,22 @@ class FusedPredictor:
             x = y
         return x
 
+    @torch.no_grad()
+    def classify(self, x: Tensor, k: int, weights: str | None = None) -> tuple[Tensor, Tensor]:
+        """The ``k`` most likely classes of every row of ``x`` (what :meth:`forward` takes; a 1-D input is
+        one row): ``(idx int32 [rows, k], logprob fp32 [rows, k])`` on the device, in rank order, by the
+        rule of :func:`..ops.functional.topk_rows_reference`. The forward kernels, then one
+        ``PF.topk_rows`` launch on the logits (csrc/topk_rows.hip); the softmax is never materialised.
+        ValueError for another head (its outputs are no distribution) and for ``k`` outside
+        ``[1, min(classes, 64)]``."""
+        fp8 = self._want_fp8(weights)
+        if self.head != "softmax":
+            raise ValueError(f"classify needs a softmax head, this model ends in {self.head!r}")
+        width = self.stages[-1].out_width
+        k = PF.check_topk(k, width)
+        logits = self._logits(x, fp8).reshape(-1, width)
+        return PF.topk_rows(logits, k)
+
     # ------------------------------------------------------------------------------------
     # token generation
     # ------------------------------------------------------------------------------------
@@ -320,7 +340,8 @@ class FusedPredictor:
     # sequence scoring (csrc/token_logprob.hip)
     # ------------------------------------------------------------------------------------
     @torch.no_grad()
-    def score(self, seq: Tensor, weights: str | None = None, chunk_rows: int | None = None) -> tuple[Tensor, Tensor]:
+    def score(self, seq: Tensor, weights: str | None = None, chunk_rows: int | None = None,
+              top_logprobs: int | None = None) -> tuple:
         """``seq``: int ids ``[R, W]`` with ``W > L`` = :attr:`context_length`. Returns ``(logprob fp32
         [R, W - L], rank int32 [R, W - L])`` on the device: entry ``[r, j]`` is the log-probability and the
         rank (0 = the most likely class) of ``seq[r, L + j]`` under the distribution the model gives the
@@ -329,7 +350,12 @@ class FusedPredictor:
         One upload, one range check (window ids as ``PF.embedding`` takes them, scored ids in
         ``[0, classes)``), then per chunk of ``chunk_rows`` windows (default: as many as keep a chunk's
         fp32 logits within ``SCORE_LOGITS_BYTES``) the forward kernels and one ``PF.token_logprob`` launch
-        that writes its slice of the results; nothing is read back inside the loop."""
+        that writes its slice of the results; nothing is read back inside the loop.
+
+        ``top_logprobs=k`` (``1 <= k <= min(classes, 64)``) adds one ``PF.topk_rows`` launch per chunk on the
+        same logits and returns ``(logprob, rank, top_idx int32 [R, W - L, k], top_logprob fp32 [R, W - L, k])``:
+        what the model would have preferred at every scored position, in rank order. Unset, the call makes
+        the launches and returns the two tensors it always did."""
         fp8 = self._want_fp8(weights)
         reason = self.generation_unsupported()
         if reason is not None:
@@ -343,12 +369,17 @@ class FusedPredictor:
             chunk_rows = max(1, SCORE_LOGITS_BYTES // (4 * width))
         if isinstance(chunk_rows, bool) or not isinstance(chunk_rows, int) or chunk_rows < 1:
             raise ValueError(f"chunk_rows must be an integer >= 1, got {chunk_rows!r}")
+        k = None if top_logprobs is None else PF.check_topk(top_logprobs, width, "top_logprobs")
         seq = seq.to(device=self.dev, dtype=torch.int64)
         rows, scored = seq.shape[0], seq.shape[1] - length
         logprob = torch.empty(rows, scored, device=self.dev, dtype=torch.float32)
         rank = torch.empty(rows, scored, device=self.dev, dtype=torch.int32)
+        tops = ()
+        if k is not None:
+            tops = (torch.empty(rows, scored, k, device=self.dev, dtype=torch.int32),
+                    torch.empty(rows, scored, k, device=self.dev, dtype=torch.float32))
         if rows == 0:
-            return logprob, rank
+            return (logprob, rank) + tops
         vocab = self.store.view(self.stages[0].seg_w).shape[0]
         # once, one read (the loop skips the id check): PF.check_index_range's rule for the context columns as
         # PF.embedding takes them, and for the scored columns as classes (width <= vocab: they are valid inputs too)
@@ -365,7 +396,9 @@ class FusedPredictor:
             i1 = min(i0 + chunk_rows, rows * scored)
             logits = self._logits(windows[i0:i1], fp8, check_ids=False).reshape(i1 - i0, width)
             PF.token_logprob(logits, targets[i0:i1], lp[i0:i1], rk[i0:i1])
-        return logprob, rank
+            if k is not None:
+                PF.topk_rows(logits, k, tops[0].view(-1, k)[i0:i1], tops[1].view(-1, k)[i0:i1])
+        return (logprob, rank) + tops
 
     # ------------------------------------------------------------------------------------
     # one-launch generation (csrc/generate_resident.hip)

@@ -330,6 +330,66 @@ class NeuralNetworkModel(MultiLayerPerceptron):
                     out = out.float()
         return out.tolist()
 
+    def classify(self, input_data: list, top_k: int = 1, weights: str | None = None) -> dict:
+        """The ``top_k`` most likely classes of a softmax-head model and how sure it is of them:
+        ``{"classes": [...], "probabilities": [...]}`` in rank order (descending probability, equal logits in
+        ascending class order: the rule of :func:`..ops.functional.topk_rows_reference`). ``input_data`` as in
+        :meth:`predict`: a vector gives one flat list each, a batch one list per row.
+
+        GPU models with a fused predictor run :meth:`..engine.predictor.FusedPredictor.classify`: the
+        forward kernels and one selection launch on the logits; the softmax row is never formed, and only
+        ``[rows, top_k]`` numbers are downloaded. CPU models, the reference runtime and models without a
+        predictor run the layers in eval mode under ``no_grad`` and the pure-torch rule on the softmax
+        layer's input. ``weights="fp8"`` as in :meth:`predict`. ``ValueError`` for another head and for a
+        ``top_k`` that is no integer in ``[1, min(classes, 64)]``."""
+        from ..ops import functional as PF
+        if weights is not None:
+            if weights != "fp8":
+                raise ValueError(f"unknown weights {weights!r}: None (the model's own precision) or 'fp8'")
+            if not self.on_gpu:
+                raise ValueError("weights='fp8' needs a model on a GPU (the e4m3 kernels are HIP kernels)")
+        if not self.algos or self.algos[-1] != "softmax":
+            raise ValueError(f"model {self.model_id} cannot classify: top-k classes need a softmax head")
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 1:
+            raise ValueError(f"top_k must be an integer >= 1, got {top_k!r}")
+        x = self._input_tensor(input_data)
+        with torch.no_grad():
+            predictor = self._fused_predictor() if self.on_gpu else None
+            if weights is not None and predictor is None:
+                raise ValueError(f"weights='fp8' is not available for model {self.model_id}: "
+                                 f"{getattr(self, '_predictor_reason', 'no fused predictor')}")
+            for layer in self.layers:
+                layer.training = False
+            single = self._output_is_vector(x)
+            if predictor is not None:
+                idx, logprob = (predictor.classify(x, top_k, weights=weights) if weights is not None
+                                else predictor.classify(x, top_k))
+            else:
+                logits = self._forward(x, None)[0][-2].detach()  # the softmax layer's input
+                idx, logprob = PF.topk_rows_reference(logits, PF.check_topk(top_k, logits.shape[-1], "top_k"))
+            # one download: the classes (exact in fp64) next to their probabilities, exp of the fp64 image
+            both = torch.empty(2, *idx.shape, device=idx.device, dtype=torch.float64)
+            both[0].copy_(idx)
+            both[1].copy_(logprob)
+            both[1].exp_()
+            both = both.tolist()
+        classes = [[int(c) for c in row] for row in both[0]]
+        return {"classes": classes[0] if single else classes, "probabilities": both[1][0] if single else both[1]}
+
+    def _output_is_vector(self, x: Tensor) -> bool:
+        """Whether this input is one row without a batch dimension (a vector, or one id row whose positions
+        the flatten layers merge into one), by the dimensions the layers give it. (Not by the output's: the
+        CPU batchnorm's running statistics keep a leading 1 after a training step.)"""
+        shape = list(x.shape)
+        for layer in self.layers:
+            if layer.algo == "embedding":
+                shape.append(1)
+            elif layer.algo == "flatten" and len(shape) > 1:
+                shape[-2] //= int(layer.ratio)
+                if shape[-2] == 1:
+                    del shape[-2]
+        return len(shape) == 1
+
     def _fused_predictor(self):
         if self._predictor is None:
             from ..engine.predictor import FusedPredictor, UnsupportedModel
@@ -372,7 +432,7 @@ class NeuralNetworkModel(MultiLayerPerceptron):
     def generate(self, context: list, max_new_tokens: int, temperature: float = 1.0, top_k: int | None = None,
                  seed: int | None = None, stop_token: int | None = None, pad_token: int = 0,
                  weights: str | None = None, loop: str | None = None, top_p: float | None = None,
-                 min_p: float | None = None, logprobs: bool = False) -> dict:
+                 min_p: float | None = None, logprobs: bool = False, top_logprobs: int | None = None) -> dict:
         """Sample ``max_new_tokens`` ids after ``context`` from a next-token model (embedding first,
         softmax head): ``{"tokens": [[...], ...], "seed": int}``, one row per context row.
 
@@ -405,7 +465,12 @@ class NeuralNetworkModel(MultiLayerPerceptron):
         ``top_p`` and ``min_p`` drew it with (a token that top-k sampling drew has the probability the
         whole vocabulary leaves it). It is computed after the loop by one :meth:`score` pass over
         ``[context | tokens]`` (one batched forward, with the loop's ``weights``), and cut after
-        ``stop_token`` as the tokens are. Unset, nothing is computed and the key is absent."""
+        ``stop_token`` as the tokens are. Unset, nothing is computed and the key is absent.
+
+        ``top_logprobs=k`` (an integer in ``[1, min(classes, 64)]``, with or without ``logprobs``) adds
+        ``"top_tokens"`` and ``"top_logprobs"`` from the same pass: for every returned token the ``k`` classes
+        the model found most likely at that position, in rank order, and their log-probabilities
+        (:func:`..ops.functional.topk_rows_reference`), cut as the tokens are."""
         from ..ops import functional as PF
         if not isinstance(logprobs, bool):
             raise ValueError(f"logprobs must be a boolean, got {logprobs!r}")
@@ -431,6 +496,8 @@ class NeuralNetworkModel(MultiLayerPerceptron):
         if min_p is not None and (isinstance(min_p, bool) or not isinstance(min_p, (int, float)) or not 0 <= min_p < 1):
             raise ValueError(f"min_p must be in [0, 1), got {min_p!r}")
         extra = PF.nucleus_args(top_p, min_p)  # (only when set, as loop)
+        if top_logprobs is not None:
+            PF.check_topk(top_logprobs, classes, "top_logprobs")
         if stop_token is not None and (not isinstance(stop_token, int) or not 0 <= stop_token < classes):
             raise ValueError(f"stop_token {stop_token!r} is outside the vocabulary of {classes}")
         if not isinstance(pad_token, int) or not 0 <= pad_token < vocab:
@@ -474,18 +541,26 @@ class NeuralNetworkModel(MultiLayerPerceptron):
             else:
                 drawn = self._generate_layers(ids, max_new_tokens, float(temperature), top_k, key, stop_token, **extra)
             tokens = drawn.tolist() if isinstance(drawn, Tensor) else drawn
-            scores = None
-            if logprobs:  # one batched forward on [context | tokens], after the loop
+            scores = tops = None
+            if logprobs or top_logprobs is not None:  # one batched forward on [context | tokens], after the loop
                 full = torch.cat([ids.to(self.device), torch.as_tensor(drawn).to(self.device)], dim=1)
+                more = {} if top_logprobs is None else {"top_logprobs": top_logprobs}
                 if predictor is not None:
-                    scores = predictor.score(full, weights=weights)[0].tolist()
+                    scored = predictor.score(full, weights=weights, **more)
                 else:
-                    scores = self._score_layers(full)[0].tolist()
+                    scored = self._score_layers(full, **more)
+                if logprobs:
+                    scores = scored[0].tolist()
+                if top_logprobs is not None:
+                    tops = (scored[2].tolist(), scored[3].tolist())
         result = {"tokens": tokens, "seed": seed}
         if stop_token is not None:
             result["tokens"] = [row[:row.index(stop_token) + 1] if stop_token in row else row for row in tokens]
         if scores is not None:
             result["logprobs"] = [lp[:len(row)] for lp, row in zip(scores, result["tokens"])]
+        if tops is not None:
+            result["top_tokens"] = [t[:len(row)] for t, row in zip(tops[0], result["tokens"])]
+            result["top_logprobs"] = [t[:len(row)] for t, row in zip(tops[1], result["tokens"])]
         return result
 
     def _generate_layers(self, ids: Tensor, steps: int, temperature: float, top_k, key, stop_token, **nucleus) -> list:
@@ -509,7 +584,8 @@ class NeuralNetworkModel(MultiLayerPerceptron):
     SCORE_MAX_IDS = 1 << 24  # scored ids per call (the padded batch is one tensor on the device)
     SCORE_LAYERS_BYTES = 64 << 20  # _score_layers: the fp64 log-softmax of one chunk of windows stays within this
 
-    def score(self, sequences: list, pad_token: int = 0, weights: str | None = None, details: bool = True) -> dict:
+    def score(self, sequences: list, pad_token: int = 0, weights: str | None = None, details: bool = True,
+              top_logprobs: int | None = None) -> dict:
         """How likely a next-token model (embedding first, softmax head) finds ``sequences``: one non-empty
         id list or a non-empty batch of non-empty lists. Every id of a row is scored given the
         :attr:`context_length` ids before it; a row is left-padded with ``pad_token``, the convention of
@@ -527,7 +603,13 @@ class NeuralNetworkModel(MultiLayerPerceptron):
         forward kernels and one ``PF.token_logprob`` launch per chunk of windows). CPU models, the reference
         runtime and models without a predictor run the layer loop in eval mode under ``no_grad`` with the
         pure-torch rule. ``weights="fp8"`` as in :meth:`predict`. ``IndexError`` for an id that is not a
-        class of the model."""
+        class of the model.
+
+        ``top_logprobs=k`` (an integer in ``[1, min(classes, 64)]``; needs ``details=True``) adds
+        ``"top_tokens"`` and ``"top_logprobs"``: per row, for every scored id, the ``k`` classes the model found
+        most likely there, in rank order, and their log-probabilities
+        (:func:`..ops.functional.topk_rows_reference`; on the device one more ``PF.topk_rows`` launch per
+        chunk). ``rows x longest x k`` stays within ``SCORE_MAX_IDS``."""
         from ..ops import functional as PF
         if weights is not None:
             if weights != "fp8":
@@ -537,6 +619,10 @@ class NeuralNetworkModel(MultiLayerPerceptron):
         if not isinstance(details, bool):
             raise ValueError(f"details must be a boolean, got {details!r}")
         vocab, classes = self._generation_shape()
+        if top_logprobs is not None:
+            PF.check_topk(top_logprobs, classes, "top_logprobs")
+            if not details:
+                raise ValueError("top_logprobs needs details=True: the per-id lists are where it is reported")
         if isinstance(pad_token, bool) or not isinstance(pad_token, int) or not 0 <= pad_token < vocab:
             raise ValueError(f"pad_token {pad_token!r} is outside the vocabulary of {vocab}")
         if not isinstance(sequences, list) or not sequences:
@@ -550,6 +636,9 @@ class NeuralNetworkModel(MultiLayerPerceptron):
         if len(batch) * longest > self.SCORE_MAX_IDS:
             raise ValueError(f"too many ids to score in one call: {len(batch)} rows of up to {longest} "
                              f"(at most {self.SCORE_MAX_IDS} with the padding)")
+        if top_logprobs is not None and len(batch) * longest * top_logprobs > self.SCORE_MAX_IDS:
+            raise ValueError(f"too many top_logprobs in one call: {len(batch)} rows of up to {longest} ids, {top_logprobs} "
+                             f"each (at most {self.SCORE_MAX_IDS} with the padding)")
         # [pad] * L, the row, then zeros (masked: any class would do) up to the longest row
         ids = torch.tensor([[pad_token] * length + row + [0] * (longest - len(row)) for row in batch], dtype=torch.int64)
         valid = torch.arange(longest).unsqueeze(0) < torch.tensor(lengths).unsqueeze(1)
@@ -561,10 +650,11 @@ class NeuralNetworkModel(MultiLayerPerceptron):
                                  f"{getattr(self, '_predictor_reason', 'no fused predictor')}")
             for layer in self.layers:
                 layer.training = False
+            more = {} if top_logprobs is None else {"top_logprobs": top_logprobs}
             if predictor is not None:
-                logprob, rank = predictor.score(ids, weights=weights)
+                logprob, rank, *tops = predictor.score(ids, weights=weights, **more)
             else:
-                logprob, rank = self._score_layers(ids)
+                logprob, rank, *tops = self._score_layers(ids, **more)
             valid = valid.to(logprob.device)
             total = torch.where(valid, logprob.double(), torch.zeros((), dtype=torch.float64, device=logprob.device)).sum()
             first = ((rank == 0) & valid).sum().double()
@@ -575,11 +665,15 @@ class NeuralNetworkModel(MultiLayerPerceptron):
             if details:
                 result["logprobs"] = [row[:n] for row, n in zip(logprob.tolist(), lengths)]
                 result["ranks"] = [row[:n] for row, n in zip(rank.tolist(), lengths)]
+                if tops:
+                    result["top_tokens"] = [row[:n] for row, n in zip(tops[0].tolist(), lengths)]
+                    result["top_logprobs"] = [row[:n] for row, n in zip(tops[1].tolist(), lengths)]
         return result
 
-    def _score_layers(self, ids: Tensor) -> tuple[Tensor, Tensor]:
+    def _score_layers(self, ids: Tensor, top_logprobs: int | None = None) -> tuple:
         """The scorer through the layers (``_forward`` in eval mode) with the pure-torch rule: ``ids [R, L + n]``
-        -> ``(fp64 logprob [R, n], int64 rank [R, n])`` of the columns from ``L`` on, in chunks of windows."""
+        -> ``(fp64 logprob [R, n], int64 rank [R, n])`` of the columns from ``L`` on, in chunks of windows;
+        with ``top_logprobs=k`` also ``(int64 top_idx [R, n, k], fp64 top_logprob [R, n, k])``."""
         from ..ops import functional as PF
         rows, length = ids.shape[0], self.context_length
         scored = ids.shape[1] - length
@@ -588,13 +682,20 @@ class NeuralNetworkModel(MultiLayerPerceptron):
         targets = ids[:, length:].reshape(-1)
         classes = self._generation_shape()[1]
         chunk = max(1, self.SCORE_LAYERS_BYTES // (8 * classes))
-        logprob, rank = [], []
+        logprob, rank, top_idx, top_lp = [], [], [], []
         for i0 in range(0, rows * scored, chunk):
             logits = self._forward(windows[i0:i0 + chunk], None)[0][-2].detach()  # the softmax layer's input
             lp, rk = PF.token_logprob_reference(logits.reshape(-1, classes), targets[i0:i0 + chunk])
             logprob.append(lp)
             rank.append(rk)
-        return torch.cat(logprob).view(rows, scored), torch.cat(rank).view(rows, scored)
+            if top_logprobs is not None:
+                ti, tl = PF.topk_rows_reference(logits.reshape(-1, classes), top_logprobs)
+                top_idx.append(ti)
+                top_lp.append(tl)
+        out = (torch.cat(logprob).view(rows, scored), torch.cat(rank).view(rows, scored))
+        if top_logprobs is not None:
+            out += (torch.cat(top_idx).view(rows, scored, -1), torch.cat(top_lp).view(rows, scored, -1))
+        return out
 
     def _forward(self, input_tensor: Tensor, target: list, dropout_rate=0.0) -> Tuple[list[Tensor], Tensor]:
         target_specified = target is not None and (isinstance(target, Tensor) or all(t is not None for t in target))

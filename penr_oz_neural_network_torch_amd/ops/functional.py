@@ -616,6 +616,56 @@ def token_logprob(logits: Tensor, targets: Tensor, logprob: Tensor | None = None
     return logprob, rank
 
 
+# --------------------------------------------------------------------------------------------
+# top-k answers (csrc/topk_rows.hip)
+# --------------------------------------------------------------------------------------------
+TOPK_MAX = 64  # kTopkMaxK of csrc/pz_kernels.h
+
+
+def check_topk(k, cols: int, what: str = "k") -> int:
+    """``k`` as an int, or ValueError unless it is an integer (no boolean) in ``[1, min(cols, TOPK_MAX)]``."""
+    if cols < 1:
+        raise ValueError("logits must have at least one column")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= min(cols, TOPK_MAX):
+        raise ValueError(f"{what} must be an integer in [1, min({cols}, {TOPK_MAX})] = [1, {min(cols, TOPK_MAX)}], got {k!r}")
+    return k
+
+
+def topk_rows_reference(logits: Tensor, k: int) -> tuple[Tensor, Tensor]:
+    """The rule of :func:`topk_rows` in pure torch, on CPU or GPU tensors: ``logits [rows, V]`` (or ``[V]``)
+    of any float dtype and ``1 <= k <= min(V, 64)`` -> ``(int64 idx [rows, k], fp64 logprob [rows, k])``.
+
+    * ``idx[r, j]`` is the column whose rank by :func:`token_logprob_reference` is ``j``: descending logit,
+      compared in the logits' own dtype (``-0 == +0``), equal logits in ascending column order — a stable
+      descending sort, not ``torch.topk`` (whose tie order is unspecified);
+    * ``logprob[r, j] = log_softmax(logits.double())[r, idx[r, j]]``; a ``-inf`` column that reaches the
+      top k scores ``-inf``.
+
+    ValueError for ``k`` outside ``[1, min(V, 64)]`` and for ``V < 1``."""
+    lg = logits.detach()
+    k = check_topk(k, lg.shape[-1] if lg.dim() else 0)
+    lg = lg.unsqueeze(0) if lg.dim() == 1 else lg.reshape(-1, lg.shape[-1])
+    idx = torch.sort(lg, dim=-1, descending=True, stable=True).indices[:, :k]
+    return idx, torch.log_softmax(lg.double(), dim=-1).gather(1, idx)
+
+
+def topk_rows(logits: Tensor, k: int, idx: Tensor | None = None, logprob: Tensor | None = None) -> tuple[Tensor, Tensor]:
+    """Per row of the fp32 ``logits [rows, V]`` (unit column stride, any row stride ``>= V``), the ``k``
+    most likely columns in rank order into ``idx`` (int32 ``[rows, k]``) and their log-probabilities into
+    ``logprob`` (fp32 ``[rows, k]``), by the rule of :func:`topk_rows_reference` (csrc/topk_rows.hip; one
+    launch, nothing comes back to the host). Both outputs take a unit column stride and any row stride
+    ``>= k`` and are allocated when ``None``. ``1 <= k <= min(V, 64)``. The call is bit-reproducible, a
+    row's result does not depend on the rows sent with it, and ``logprob[:, j]`` has the bits of
+    ``token_logprob(logits, idx[:, j])[0]``. The binding refuses tensors of another dtype, device or
+    shape, other strides and other ``k``; no rows is no launch."""
+    if idx is None:
+        idx = torch.empty(logits.shape[0], int(k), device=logits.device, dtype=torch.int32)
+    if logprob is None:
+        logprob = torch.empty(logits.shape[0], int(k), device=logits.device, dtype=torch.float32)
+    _ops().topk_rows(logits, int(k), idx, logprob)
+    return idx, logprob
+
+
 def check_index_range(idx: Tensor, lo: int, hi: int, what: str, size: int | None = None) -> None:
     """Raise IndexError (as ATen / Python indexing do) unless every id is in ``[lo, hi)``.
     The HIP kernels never read outside their tables either way, but a bad id must surface as an
@@ -815,4 +865,5 @@ __all__ = ["gemm", "gemm_path", "gemm_last_kernel", "gemm_skinny", "gemm_skinny_
            "gemm_skinny_plan", "gemm_skinny_w8_plan", "gemm_sk_plan",
            "quantize_cols", "quantize_cols_reference", "dequantize_cols", "linear", "activation", "dropout", "softmax", "cross_entropy", "mse_loss",
            "batchnorm", "embedding", "tensor_summary", "epi_spec", "new_seed", "sample_rows", "sample_rows_reference", "nucleus_args",
-           "sample_uniform", "generate_resident", "token_logprob", "token_logprob_reference"]
+           "sample_uniform", "generate_resident", "token_logprob", "token_logprob_reference", "topk_rows", "topk_rows_reference",
+           "check_topk", "TOPK_MAX"]
