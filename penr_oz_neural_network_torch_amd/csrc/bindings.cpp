@@ -785,11 +785,20 @@ void sample_rows_op(const Tensor& logits, const Tensor& seq, const Tensor& done,
   PZ_HIP_CHECK(pz::sample_rows(a, cur_stream(logits)));
 }
 
+// what token_logprob and topk_rows ask of their logits: fp32 [rows, V] on the GPU, rows may be strided
+void check_row_logits(const Tensor& logits, const char* who) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kFloat && logits.dim() == 2, who,
+              "logits must be a GPU fp32 [rows, V] tensor");
+  const int64_t rows = logits.size(0), cols = logits.size(1);
+  TORCH_CHECK(cols >= 1 && cols <= pz::kSampleMaxCols && rows <= INT32_MAX, who, "shape out of range: [", rows, ", ", cols, "]");
+  TORCH_CHECK(cols == 1 || logits.stride(1) == 1, who, "logits must have a unit column stride, got ", logits.stride(1));
+  TORCH_CHECK(rows <= 1 || logits.stride(0) >= cols, who, "logits rows overlap: row stride ", logits.stride(0), " < V = ", cols);
+}
+
 // the log-probability and the rank of targets[r] under row r of the logits (csrc/token_logprob.hip)
 void token_logprob_op(const Tensor& logits, const Tensor& targets, const Tensor& logprob, const optional<Tensor>& rank) {
   const char* who = "pz::token_logprob: ";
-  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kFloat && logits.dim() == 2, who,
-              "logits must be a GPU fp32 [rows, V] tensor");
+  check_row_logits(logits, who);
   TORCH_CHECK(targets.is_cuda() && targets.scalar_type() == at::kLong && targets.dim() == 1, who,
               "targets must be a GPU int64 [rows] tensor");
   TORCH_CHECK(logprob.is_cuda() && logprob.scalar_type() == at::kFloat && logprob.dim() == 1, who,
@@ -804,9 +813,6 @@ void token_logprob_op(const Tensor& logits, const Tensor& targets, const Tensor&
   TORCH_CHECK(targets.device() == logits.device() && logprob.device() == logits.device() &&
                   (!has_rank || rank->device() == logits.device()),
               who, "every tensor must be on the logits' device");
-  TORCH_CHECK(cols >= 1 && cols <= pz::kSampleMaxCols && rows <= INT32_MAX, who, "shape out of range: [", rows, ", ", cols, "]");
-  TORCH_CHECK(cols == 1 || logits.stride(1) == 1, who, "logits must have a unit column stride, got ", logits.stride(1));
-  TORCH_CHECK(rows <= 1 || logits.stride(0) >= cols, who, "logits rows overlap: row stride ", logits.stride(0), " < V = ", cols);
   if (rows == 0) return;
   pz::TokenLogprobArgs a{};
   a.logits = logits.data_ptr<float>();
@@ -825,13 +831,11 @@ void token_logprob_op(const Tensor& logits, const Tensor& targets, const Tensor&
 // the k most likely columns of every row of the logits, in rank order, and their log-probabilities (csrc/topk_rows.hip)
 void topk_rows_op(const Tensor& logits, int64_t k, const Tensor& idx, const Tensor& logprob) {
   const char* who = "pz::topk_rows: ";
-  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kFloat && logits.dim() == 2, who,
-              "logits must be a GPU fp32 [rows, V] tensor");
+  check_row_logits(logits, who);
   TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == at::kInt && idx.dim() == 2, who, "idx must be a GPU int32 [rows, k] tensor");
   TORCH_CHECK(logprob.is_cuda() && logprob.scalar_type() == at::kFloat && logprob.dim() == 2, who,
               "logprob must be a GPU fp32 [rows, k] tensor");
   const int64_t rows = logits.size(0), cols = logits.size(1);
-  TORCH_CHECK(cols >= 1 && cols <= pz::kSampleMaxCols && rows <= INT32_MAX, who, "shape out of range: [", rows, ", ", cols, "]");
   TORCH_CHECK(k >= 1 && k <= std::min<int64_t>(cols, pz::kTopkMaxK), who, "k must be in [1, min(V, ", pz::kTopkMaxK,
               ")] = [1, ", std::min<int64_t>(cols, pz::kTopkMaxK), "], got ", k);
   TORCH_CHECK(idx.size(0) == rows && idx.size(1) == k && logprob.size(0) == rows && logprob.size(1) == k, who,
@@ -839,8 +843,6 @@ void topk_rows_op(const Tensor& logits, int64_t k, const Tensor& idx, const Tens
               logprob.size(0), ", ", logprob.size(1), "]");
   TORCH_CHECK(idx.device() == logits.device() && logprob.device() == logits.device(), who,
               "every tensor must be on the logits' device");
-  TORCH_CHECK(cols == 1 || logits.stride(1) == 1, who, "logits must have a unit column stride, got ", logits.stride(1));
-  TORCH_CHECK(rows <= 1 || logits.stride(0) >= cols, who, "logits rows overlap: row stride ", logits.stride(0), " < V = ", cols);
   TORCH_CHECK(k == 1 || (idx.stride(1) == 1 && logprob.stride(1) == 1), who, "idx and logprob must have a unit column stride, got ",
               idx.stride(1), " and ", logprob.stride(1));
   TORCH_CHECK(rows <= 1 || (idx.stride(0) >= k && logprob.stride(0) >= k), who, "output rows overlap: row strides ",

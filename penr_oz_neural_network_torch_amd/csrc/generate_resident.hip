@@ -44,10 +44,10 @@
 // 168 VGPRs, the min-p compare in every weight), and a request with them gives up a third of the
 // occupancy (2 instead of 3 waves/SIMD) only where it asks for the select.
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
-//   <bf16, false>  168 VGPRs, 0 AGPRs, 106 SGPRs (63 spilled to VGPR lanes), scratch 0, static LDS 0, occupancy 3 waves/SIMD
+//   <bf16, false>  168 VGPRs, 0 AGPRs, 106 SGPRs (65 spilled to VGPR lanes), scratch 0, static LDS 0, occupancy 3 waves/SIMD
 //   <fp32, false>  166 VGPRs, 0 AGPRs, 106 SGPRs (65 spilled to VGPR lanes), scratch 0, static LDS 0, occupancy 3 waves/SIMD
 //   <bf16, true>   206 VGPRs, 0 AGPRs, 106 SGPRs (80 spilled to VGPR lanes), scratch 0, static LDS 0, occupancy 2 waves/SIMD
-//   <fp32, true>   204 VGPRs, 0 AGPRs, 106 SGPRs (80 spilled to VGPR lanes), scratch 0, static LDS 0, occupancy 2 waves/SIMD
+//   <fp32, true>   204 VGPRs, 0 AGPRs, 106 SGPRs (81 spilled to VGPR lanes), scratch 0, static LDS 0, occupancy 2 waves/SIMD
 // Dynamic LDS = the plan's total: 28,608 B (bf16) / 36,160 B (fp32) for the character model
 // [27, 10, 30, 64, 27], so registers (3 workgroups per CU), not LDS, bound its residency; one
 // workgroup per CU once a plan passes 80 KiB.

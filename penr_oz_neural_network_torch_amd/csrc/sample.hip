@@ -14,8 +14,8 @@
 //     the row maximum and the lowest index holding it. temperature == 0 stops here.
 //  2. top-k threshold (0 < top_k < V): an exact radix select on the keys, digits of 12, 10 and 10
 //     bits from the top, each pass an LDS histogram of the columns that match the digits found so
-//     far and a suffix scan over the bins (12 bits first: sign, exponent and 3 mantissa bits spread
-//     logits of one octave over 8 bins, which keeps same-address LDS atomics short). Integer
+//     far and a suffix scan over the bins (row_core.h: pick_digit; 12 bits first: sign, exponent and 3
+//     mantissa bits spread logits of one octave over 8 bins: short same-address LDS atomics). Integer
 //     arithmetic only: the k-th largest key comes out exactly, columns with key >= it are kept
 //     (ties at the threshold all stay).
 //  2b. min-p (0 < min_p < 1) drops the kept columns with w_c < min_p; top-p (0 < top_p < 1) then keeps

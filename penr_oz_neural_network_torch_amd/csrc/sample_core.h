@@ -11,17 +11,12 @@
 // call's first write goes to best_w.
 #pragma once
 
-#include "pz_common.h"
-#include "pz_kernels.h"
+#include "row_core.h"
 
 namespace pz {
 
 constexpr int kSegments = 64;      // one per lane of the selecting wave
 constexpr int kSampleMaxWaves = 16;
-constexpr int kSampleLoads = 16;   // loads in flight per thread
-constexpr int kDigits = 3;         // key digits from the top: 12, 10 and 10 bits
-constexpr int kMaxBins = 1 << 12;
-constexpr int kBins = 1 << 10;
 constexpr int kMassBins = 1 << 11;  // 64-bit bins in hist; nucleus digits from the top: 11, 11 and 10 bits
 
 // the LDS a workgroup needs for one row (16.5 KiB), wherever the kernel keeps it. The nucleus select
@@ -46,38 +41,6 @@ struct alignas(16) SampleScratch {
 static_assert(sizeof(SampleScratch) == kSampleScratchBytes, "pz_kernels.h: kSampleScratchBytes");
 static_assert(sizeof(int) * kMaxBins == sizeof(unsigned long long) * kMassBins, "hist as 64-bit bins");
 
-// order-preserving image of a float: a > b (as floats, -0 == +0) <=> okey(a) > okey(b)
-PZ_DEV uint32_t okey(float x) {
-  uint32_t u = __float_as_uint(x);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-PZ_DEV float okey_inv(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
-
-template <typename T>
-PZ_DEV T scan_incl(T v, int lane) {
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const T t = __shfl_up(v, d, kWave);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
-
-// f(c, x[c]) for c = first, first + stride, ... < n (any order-free fold): kSampleLoads loads, then their uses
-template <class F>
-PZ_DEV void for_strided(const float* __restrict__ x, int first, int stride, int n, F f) {
-  int c = first;
-  for (; static_cast<int64_t>(c) + static_cast<int64_t>(kSampleLoads - 1) * stride < n; c += kSampleLoads * stride) {
-    float v[kSampleLoads];
-#pragma unroll
-    for (int k = 0; k < kSampleLoads; ++k) v[k] = x[c + k * stride];
-#pragma unroll
-    for (int k = 0; k < kSampleLoads; ++k) f(c + k * stride, v[k]);
-  }
-  for (; c < n; c += stride) f(c, x[c]);
-}
-
 // kMinP false: the weigher of a call without min-p, with no trace of it in the instructions
 template <bool kMinP>
 struct Weigher {
@@ -100,14 +63,13 @@ struct Weigher {
 // weigh: the top-k threshold and min_p, nucleus off. Every thread calls it; 4 barriers per digit.
 template <int NT>
 PZ_DEV uint32_t nucleus_key(const float* __restrict__ x, int V, const Weigher<true>& weigh, float top_p, SampleScratch& sm) {
-  constexpr int kWaves = NT / kWave;
   static_assert(kMassBins % NT == 0, "block shape");
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+  const int tid = threadIdx.x;
   uint32_t prefix = 0u, mask = 0u;
   unsigned long long rem = 0ull;
 #pragma unroll
   for (int d = 0; d < kDigits; ++d) {
-    const int shift = d == 0 ? 21 : d == 1 ? 10 : 0, bins = d == 2 ? kBins : kMassBins, per = bins / NT;
+    const int shift = d == 0 ? 21 : d == 1 ? 10 : 0, bins = d == 2 ? kBins : kMassBins;
     for (int b = tid; b < bins; b += NT) sm.hist64[b] = 0ull;
     // a row without mass (all NaN) has no finder: digit 0 and rem 0 then stand through every pass. Only before
     // the first pass: later passes' readers of sel64 have no barrier between their read and this point.
@@ -123,40 +85,14 @@ PZ_DEV uint32_t nucleus_key(const float* __restrict__ x, int V, const Weigher<tr
       }
     });
     __syncthreads();
-    const int top = bins - 1 - tid * per;  // thread t owns the `per` bins below bins - t * per, descending
-    unsigned long long mine = 0ull;
-    for (int j = 0; j < per; ++j) mine += sm.hist64[top - j];
-    unsigned long long incl = scan_incl(mine, lane);
-    if (lane == kWave - 1) sm.wtot64[wave] = incl;
-    __syncthreads();
-    unsigned long long total = 0ull;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      const unsigned long long t = sm.wtot64[w];
-      incl += w < wave ? t : 0ull;
-      total += t;
-    }
-    if (d == 0) {
+    // the target, once the first pass knows the row's mass (no thread's bins cross it when total == 0)
+    auto target = [&](unsigned long long total, unsigned long long r) {
+      if (d != 0) return r;
       const double want = ceil(static_cast<double>(top_p) * static_cast<double>(total));
-      rem = want >= static_cast<double>(total) ? total : static_cast<unsigned long long>(want);
-      rem = rem < 1ull ? 1ull : rem;
-    }
-    unsigned long long run = incl - mine;
-    if (run < rem && rem <= incl) {  // exactly one thread (none when total == 0)
-      for (int j = 0; j < per; ++j) {
-        const unsigned long long h = sm.hist64[top - j];
-        if (run + h >= rem) {
-          sm.sel64[0] = static_cast<unsigned long long>(top - j);
-          sm.sel64[1] = rem - run;
-          break;
-        }
-        run += h;
-      }
-    }
-    __syncthreads();
-    prefix |= static_cast<uint32_t>(sm.sel64[0]) << shift;
-    mask |= static_cast<uint32_t>(bins - 1) << shift;
-    rem = sm.sel64[1];
+      r = want >= static_cast<double>(total) ? total : static_cast<unsigned long long>(want);
+      return r < 1ull ? 1ull : r;
+    };
+    pick_digit<NT>(sm.hist64, sm.wtot64, sm.sel64, shift, bins, prefix, mask, rem, target);
   }
   return prefix;
 }
@@ -174,21 +110,17 @@ PZ_DEV int sample_row(const float* __restrict__ x, int V, float temperature, int
   // 1. row maximum and the lowest index among the maxima
   unsigned long long best = 0ull;
   for_strided(x, tid, NT, V, [&](int c, float l) {
-    const unsigned long long p = (static_cast<unsigned long long>(okey(l)) << 32) | (0xFFFFFFFFu - static_cast<uint32_t>(c));
+    const unsigned long long p = pack_col(l, c);
     best = p > best ? p : best;
   });
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long t = __shfl_xor(best, o, kWave);
-    best = t > best ? t : best;
-  }
+  best = group_max_u64<kWave>(best);
   if (lane == 0) sm.best_w[wave] = best;
   __syncthreads();
   best = sm.best_w[0];
 #pragma unroll
   for (int w = 1; w < kWaves; ++w) best = sm.best_w[w] > best ? sm.best_w[w] : best;
-  const uint32_t kmax = static_cast<uint32_t>(best >> 32);
-  const int argmax = static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(best));
+  const uint32_t kmax = packed_key(best);
+  const int argmax = packed_col(best);
 
   int token = argmax;
   if (temperature > 0.f) {
@@ -199,7 +131,7 @@ PZ_DEV int sample_row(const float* __restrict__ x, int V, float temperature, int
       int krem = top_k;
 #pragma unroll
       for (int d = 0; d < kDigits; ++d) {
-        const int shift = d == 0 ? 20 : d == 1 ? 10 : 0, bins = d == 0 ? kMaxBins : kBins, per = bins / NT;
+        const int shift = d == 0 ? 20 : d == 1 ? 10 : 0, bins = d == 0 ? kMaxBins : kBins;
         for (int b = tid; b < bins; b += NT) sm.hist[b] = 0;
         __syncthreads();
         for_strided(x, tid, NT, V, [&](int, float l) {
@@ -207,31 +139,7 @@ PZ_DEV int sample_row(const float* __restrict__ x, int V, float temperature, int
           if ((k & mask) == prefix) atomicAdd(&sm.hist[(k >> shift) & (bins - 1)], 1);
         });
         __syncthreads();
-        // thread t owns the `per` bins below bins - t * per, descending: a prefix scan over the threads is
-        // a suffix count over the digits
-        const int top = bins - 1 - tid * per;
-        int mine = 0;
-        for (int j = 0; j < per; ++j) mine += sm.hist[top - j];
-        int incl = scan_incl(mine, lane);
-        if (lane == kWave - 1) sm.wtot[wave] = incl;
-        __syncthreads();
-        for (int w = 0; w < wave; ++w) incl += sm.wtot[w];
-        int run = incl - mine;
-        if (run < krem && krem <= incl) {  // exactly one thread: it holds the digit of the k-th largest
-          for (int j = 0; j < per; ++j) {
-            const int h = sm.hist[top - j];
-            if (run + h >= krem) {
-              sm.sel[0] = top - j;
-              sm.sel[1] = krem - run;
-              break;
-            }
-            run += h;
-          }
-        }
-        __syncthreads();
-        prefix |= static_cast<uint32_t>(sm.sel[0]) << shift;
-        mask |= static_cast<uint32_t>(bins - 1) << shift;
-        krem = sm.sel[1];
+        pick_digit<NT>(sm.hist, sm.wtot, sm.sel, shift, bins, prefix, mask, krem);
       }
       thr = prefix;
     }

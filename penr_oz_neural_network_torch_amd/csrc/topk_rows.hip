@@ -4,13 +4,13 @@
 //
 // Per row: idx[j] is the column of rank j under token_logprob.hip's rule, rank(t) = #{c : l_c > l_t} +
 // #{c < t : l_c == l_t} (-0 == +0): descending logit, then ascending column, also across ties at the k-th
-// place. The selection compares okey() images (sample_core.h) and column numbers only: integers, exact.
-// logprob[j] = (l_idx[j] - max) - logf(S), with max and S = sum_c __expf(l_c - max) formed exactly as
-// token_logprob.hip forms them for this V (its SUMMATION ORDER, restated below), so logprob[:, j] has the
-// bits of pz::token_logprob(logits, idx[:, j]). The winner's logit is okey_inv(its key): the logit itself
-// except that -0 comes back as +0, which changes no bit of the result (with max != 0 the difference
-// absorbs it; with max == +-0 and logf(S) != 0 the final subtraction does; logf(S) == 0 has one column at
-// the maximum, itself the winner, and -0 - -0 == +0 - -0 == +0).
+// place. The selection compares okey() images (row_core.h) and column numbers only: integers, exact.
+// logprob[j] = (l_idx[j] - max) - logf(S), with max and S = sum_c __expf(l_c - max) formed by the code that
+// forms them in token_logprob.hip (row_core.h: LaneRow, block_max, the wave sums and their SUMMATION ORDER),
+// so logprob[:, j] has the bits of pz::token_logprob(logits, idx[:, j]). The winner's logit is
+// okey_inv(its key): the logit itself except that -0 comes back as +0, which changes no bit of the result
+// (with max != 0 the difference absorbs it; with max == +-0 and logf(S) != 0 the final subtraction does;
+// logf(S) == 0 has one column at the maximum, itself the winner, and -0 - -0 == +0 - -0 == +0).
 //
 // The form is chosen by V alone (a row's bits never depend on the row count or on its neighbours):
 //
@@ -23,8 +23,8 @@
 //              1. maximum, and the histogram of the keys' top 12 bits (LDS integer atomics);
 //              2. S, and the histogram of the next 10 bits among the keys that match so far; 3. the last
 //                 10 bits: `thr` is the k-th largest key exactly, `need` >= 1 of the columns at thr are
-//                 wanted besides the k - need columns above it (the radix select of sample_core.h, which
-//                 lives inside sample_row there; restated here so that the sampler's code stays as it is);
+//                 wanted besides the k - need columns above it (the radix select of the sampler:
+//                 row_core.h's pick_digit);
 //              4. wave w walks its contiguous share of the row's 64-column chunks in column order: a
 //                 column above thr takes the next free candidate slot (one LDS integer counter: arrival
 //                 order), the columns at thr are counted per wave;
@@ -37,110 +37,50 @@
 //              The row is read five times (the later reads come from the caches); steps 4 and 5 issue
 //              coalesced 4-byte loads, step 4 kTkLoads of them before their uses.
 //
-// SUMMATION ORDER of S, as token_logprob.hip (G = 16, 64, 256 or 1024 lanes / threads share a row): lane l
-// adds its columns l, l + G, ... in column order (onto its first column in the register forms, onto 0 in
-// the workgroup forms); a DPP row of 16 folds as row16_reduce, the four rows of a wave as (r0 + r1) +
-// (r2 + r3); the workgroup forms fold the wave sums, zeros behind them, once more in the same way.
-//
 // logits rows may be strided (row stride >= V, unit column stride); idx and logprob rows may be strided
 // (row stride >= k, unit column stride). No global scratch, no float atomics, nothing leaves the workgroup.
 //
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage), no scratch:
-//   topk_rows_lanes_kernel<16>  26 VGPRs, 0 B LDS     topk_rows_block_kernel<256>   46 VGPRs, 16,972 B LDS
-//   topk_rows_lanes_kernel<64>  52 VGPRs, 0 B LDS     topk_rows_block_kernel<1024>  52 VGPRs, 17,164 B LDS
-#include <cmath>
-
-#include "sample_core.h"
+//   topk_rows_lanes_kernel<16>  26 VGPRs, 0 B LDS     topk_rows_block_kernel<256>   42 VGPRs, 16,972 B LDS
+//   topk_rows_lanes_kernel<64>  52 VGPRs, 0 B LDS     topk_rows_block_kernel<1024>  51 VGPRs, 17,164 B LDS
+#include "row_core.h"
 
 namespace pz {
 namespace {
 
-constexpr int kTkThreads = 256;
-constexpr int kTkGroupCols = 64;  // up to here 16 lanes own a row
-constexpr int kTkLoads = 8;       // chunk loads in flight per lane in the compaction walk
+constexpr int kTkLoads = 8;  // chunk loads in flight per lane in the compaction walk
 
-PZ_DEV unsigned long long tk_pack(float l, int c) {
-  return (static_cast<unsigned long long>(okey(l)) << 32) | (0xFFFFFFFFu - static_cast<uint32_t>(c));
-}
-
-// the maximum over the G lanes that share a row (xor offsets below G stay inside the group)
 template <int G>
-PZ_DEV unsigned long long group_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) {
-    const unsigned long long t = __shfl_xor(v, o, kWave);
-    v = t > v ? t : v;
-  }
-  return v;
-}
+__global__ void __launch_bounds__(kRowThreads) topk_rows_lanes_kernel(TopkRowsArgs a) {
+  constexpr int kPer = LaneRow<G>::kPer;
+  LaneRow<G> r(a.rows);
+  const int V = a.cols, lane = r.lane;
 
-template <int G, typename Op>
-PZ_DEV float tk_group_reduce(float v, Op op) {
-  if constexpr (G == 16)
-    return row16_reduce(v, op);
-  else
-    return wave_reduce(v, op);
-}
-
-// G lanes per row (16: one DPP row, V <= 64; 64: the wave, V <= 1024); kPer columns per lane
-template <int G>
-__global__ void __launch_bounds__(kTkThreads) topk_rows_lanes_kernel(TopkRowsArgs a) {
-  constexpr int kPer = (G == 16 ? kTkGroupCols : kTokenLogprobWaveCols) / G;
-  constexpr int kRowsPerBlock = kTkThreads / G;
-  const int lane = threadIdx.x & (G - 1);
-  const int64_t row_raw = static_cast<int64_t>(blockIdx.x) * kRowsPerBlock + threadIdx.x / G;
-  const bool live = row_raw < a.rows;                // (whole groups; a dead group recomputes the last row, stores nothing)
-  const int64_t row = live ? row_raw : a.rows - 1;
-  const int V = a.cols;
-  const float* __restrict__ x = a.logits + row * a.ld;
-
-  float v[kPer];
-  float mx = -INFINITY;
   uint32_t alive = 0u;  // bit k: column k * G + lane exists and has not been taken
-#pragma unroll
-  for (int k = 0; k < kPer; ++k) {
-    v[k] = -INFINITY;
-    if (k * G < V) {  // wave-uniform
-      const int c = k * G + lane;
-      if (c < V) {
-        v[k] = x[c];
-        alive |= 1u << k;
-      }
-      mx = fmaxf(mx, v[k]);
-    }
-  }
-  mx = tk_group_reduce<G>(mx, OpMax{});
-  float s = lane < V ? __expf(v[0] - mx) : 0.f;
-#pragma unroll
-  for (int k = 1; k < kPer; ++k)
-    if (k * G < V) {
-      const int c = k * G + lane;
-      s += c < V ? __expf(v[k] - mx) : 0.f;
-    }
-  s = tk_group_reduce<G>(s, OpAdd{});
-  const float lse = logf(s);
+  const float mx = r.load(a.logits + r.row * a.ld, V, [&](int k, int, float) { alive |= 1u << k; });
+  const float lse = logf(r.sum_exp(V, mx, [](int, int, float) {}));
 
-  auto lane_best = [&]() {  // (0: nothing left; a live column packs to more than 0)
+  auto lane_best = [&]() {  // (0: nothing left)
     unsigned long long b = 0ull;
 #pragma unroll
     for (int k = 0; k < kPer; ++k)
       if (k * G < V) {
-        const unsigned long long p = ((alive >> k) & 1u) ? tk_pack(v[k], k * G + lane) : 0ull;
+        const unsigned long long p = ((alive >> k) & 1u) ? pack_col(r.v[k], k * G + lane) : 0ull;
         b = p > b ? p : b;
       }
     return b;
   };
-  int* __restrict__ idx = a.idx + row * a.idx_ld;
-  float* __restrict__ logprob = a.logprob + row * a.logprob_ld;
+  int* __restrict__ idx = a.idx + r.row * a.idx_ld;
+  float* __restrict__ logprob = a.logprob + r.row * a.logprob_ld;
   unsigned long long mine = lane_best();
   for (int j = 0; j < a.k; ++j) {
     const unsigned long long win = group_max_u64<G>(mine);
-    const int c = static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(win));
+    const int c = packed_col(win);
     if (win == mine && win != 0ull) {  // the one lane that holds column c
       alive &= ~(1u << (c / G));
-      if (live) {
+      if (r.live) {
         idx[j] = c;
-        logprob[j] = (okey_inv(static_cast<uint32_t>(win >> 32)) - mx) - lse;
+        logprob[j] = (okey_inv(packed_key(win)) - mx) - lse;
       }
       mine = lane_best();
     }
@@ -150,7 +90,7 @@ __global__ void __launch_bounds__(kTkThreads) topk_rows_lanes_kernel(TopkRowsArg
 template <int NT>
 __global__ void __launch_bounds__(NT) topk_rows_block_kernel(TopkRowsArgs a) {
   constexpr int kWaves = NT / kWave;
-  static_assert(NT % kWave == 0 && kWaves <= kSampleMaxWaves && kBins % NT == 0 && kMaxBins % NT == 0, "block shape");
+  static_assert(NT % kWave == 0 && kBins % NT == 0 && kMaxBins % NT == 0, "block shape");
   __shared__ int hist[kMaxBins];
   __shared__ float red_m[kWaves];
   __shared__ float red_s[kWaves];
@@ -164,38 +104,8 @@ __global__ void __launch_bounds__(NT) topk_rows_block_kernel(TopkRowsArgs a) {
   const int64_t row = blockIdx.x;
   const int V = a.cols, K = a.k;
   const float* __restrict__ x = a.logits + row * a.ld;
-
-  // after a digit's histogram is complete (a barrier behind it): the digit of the krem-th largest key
-  // among the keys that match `prefix` under `mask`, and how many of that digit's keys are still wanted.
-  // Thread t owns the `per` bins below bins - t * per, descending: a prefix scan over the threads is a
-  // suffix count over the digits.
   uint32_t prefix = 0u, mask = 0u;
   int krem = K;
-  auto pick_digit = [&](int shift, int bins) {
-    const int per = bins / NT, top = bins - 1 - tid * per;
-    int mine = 0;
-    for (int j = 0; j < per; ++j) mine += hist[top - j];
-    int incl = scan_incl(mine, lane);
-    if (lane == kWave - 1) wtot[wave] = incl;
-    __syncthreads();
-    for (int w = 0; w < wave; ++w) incl += wtot[w];
-    int run = incl - mine;
-    if (run < krem && krem <= incl) {  // exactly one thread (k <= V)
-      for (int j = 0; j < per; ++j) {
-        const int h = hist[top - j];
-        if (run + h >= krem) {
-          sel[0] = top - j;
-          sel[1] = krem - run;
-          break;
-        }
-        run += h;
-      }
-    }
-    __syncthreads();
-    prefix |= static_cast<uint32_t>(sel[0]) << shift;
-    mask |= static_cast<uint32_t>(bins - 1) << shift;
-    krem = sel[1];
-  };
 
   // 1. the maximum; the top 12 bits
   for (int b = tid; b < kMaxBins; b += NT) hist[b] = 0;
@@ -210,11 +120,8 @@ __global__ void __launch_bounds__(NT) topk_rows_block_kernel(TopkRowsArgs a) {
     mx = fmaxf(mx, l);
     atomicAdd(&hist[okey(l) >> 20], 1);
   });
-  mx = wave_max(mx);
-  if (lane == 0) red_m[wave] = mx;
-  __syncthreads();
-  mx = wave_max(lane < kWaves ? red_m[lane] : -INFINITY);
-  pick_digit(20, kMaxBins);
+  mx = block_max<NT>(mx, red_m);  // (its barrier completes the histogram)
+  pick_digit<NT>(hist, wtot, sel, 20, kMaxBins, prefix, mask, krem);
 
   // 2. S; the next 10 bits
   for (int b = tid; b < kBins; b += NT) hist[b] = 0;
@@ -225,10 +132,9 @@ __global__ void __launch_bounds__(NT) topk_rows_block_kernel(TopkRowsArgs a) {
     const uint32_t key = okey(l);
     if ((key & mask) == prefix) atomicAdd(&hist[(key >> 10) & (kBins - 1)], 1);
   });
-  s = wave_sum(s);
-  if (lane == 0) red_s[wave] = s;
+  wave_sums_put(s, red_s);
   __syncthreads();
-  pick_digit(10, kBins);
+  pick_digit<NT>(hist, wtot, sel, 10, kBins, prefix, mask, krem);
 
   // 3. the last 10 bits
   for (int b = tid; b < kBins; b += NT) hist[b] = 0;
@@ -238,7 +144,7 @@ __global__ void __launch_bounds__(NT) topk_rows_block_kernel(TopkRowsArgs a) {
     if ((key & mask) == prefix) atomicAdd(&hist[key & (kBins - 1)], 1);
   });
   __syncthreads();
-  pick_digit(0, kBins);
+  pick_digit<NT>(hist, wtot, sel, 0, kBins, prefix, mask, krem);
   const uint32_t thr = prefix;
   const int need = min(max(krem, 1), K), above = K - need;  // (1 <= krem <= K by construction)
 
@@ -289,8 +195,7 @@ __global__ void __launch_bounds__(NT) topk_rows_block_kernel(TopkRowsArgs a) {
 
   // 6. every candidate to its rank
   if (wave == 0) {
-    s = wave_sum(lane < kWaves ? red_s[lane] : 0.f);
-    const float lse = logf(s);
+    const float lse = logf(wave_sums_fold<NT>(red_s));
     if (lane < K) {
       const uint32_t key = cand_key[lane];
       const int col = cand_col[lane];
@@ -310,20 +215,8 @@ __global__ void __launch_bounds__(NT) topk_rows_block_kernel(TopkRowsArgs a) {
 hipError_t topk_rows(const TopkRowsArgs& a, hipStream_t s) {
   if (a.rows <= 0) return hipSuccess;
   if (a.cols <= 0 || a.cols > kSampleMaxCols || a.k < 1 || a.k > kTopkMaxK || a.k > a.cols) return hipErrorInvalidValue;
-  if (a.cols <= kTkGroupCols) {
-    constexpr int kRows = kTkThreads / 16;
-    hipLaunchKernelGGL(topk_rows_lanes_kernel<16>, dim3(static_cast<unsigned>((a.rows + kRows - 1) / kRows)),
-                       dim3(kTkThreads), 0, s, a);
-  } else if (a.cols <= kTokenLogprobWaveCols) {
-    constexpr int kRows = kTkThreads / kWave;
-    hipLaunchKernelGGL(topk_rows_lanes_kernel<kWave>, dim3(static_cast<unsigned>((a.rows + kRows - 1) / kRows)),
-                       dim3(kTkThreads), 0, s, a);
-  } else if (a.cols <= kSampleNarrowCols) {
-    hipLaunchKernelGGL(topk_rows_block_kernel<256>, dim3(static_cast<unsigned>(a.rows)), dim3(256), 0, s, a);
-  } else {
-    hipLaunchKernelGGL(topk_rows_block_kernel<1024>, dim3(static_cast<unsigned>(a.rows)), dim3(1024), 0, s, a);
-  }
-  return hipGetLastError();
+  return launch_row_forms(topk_rows_lanes_kernel<16>, topk_rows_lanes_kernel<kWave>, topk_rows_block_kernel<256>,
+                          topk_rows_block_kernel<1024>, a, s);
 }
 
 }  // namespace pz
